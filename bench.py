@@ -20,7 +20,15 @@ step is the same iteration, whatever --steps / --warmup the driver passes.
 
 value = env-steps of all ranks / max-over-ranks wall time of the K timed steps.
 
+A plain run does only what that figure needs: engine, regime iterations, snapshot, warm-up, the
+K timed steps, the result line.  `--full` adds everything else the benchmark measures, each in
+runs of its own around the timed steps: the CPU baseline, the rollout and update rooflines
+(per-launch event iteration, gradient bursts, counting replay), the one-rank RCCL timing, the
+other BASELINE shapes and the detail file.  `--dump-outputs DIR` writes what the last timed
+step computed as DIR/<name>.npy (float32), for comparing two builds output for output.
+
   python bench.py [--gpus N --steps K --warmup W --walkers-global 65536 --horizon 64]
+  python bench.py --full
   torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 """
 import argparse
@@ -71,6 +79,14 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline figure: the CPU baseline, the "
+                        "rollout / update rooflines, the one-rank RCCL timing, the other BASELINE "
+                        "shapes (see --no-extras, --no-cpu-baseline), and write the detail file")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the last timed step computed (weights, "
+                        "Adam moments, and the trajectory and walker records of a fixed seeded "
+                        "sample of walkers) as DIR/<name>.npy in float32")
     p.add_argument("--walkers-global", type=int, default=65536,
                    help="walkers over all GPUs (strong scaling, BASELINE config 4)")
     p.add_argument("--walkers", type=int, default=0,
@@ -86,9 +102,10 @@ def parse():
     p.add_argument("--regime-iters", type=int, default=8,
                    help="PPO iterations from the seeded start before the snapshot")
     p.add_argument("--no-extras", action="store_true",
-                   help="skip the configs 2 / 3 / 4-shard / 5-shard lines (N = 1 only)")
+                   help="with --full: skip the configs 2 / 3 / 4-shard / 5-shard lines (N = 1 only)")
     p.add_argument("--cpu-baseline-steps", type=int, default=150000)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="with --full: skip the CPU baseline")
     p.add_argument("--cpu-threads", type=int, default=0,
                    help="processes of the all-cores CPU baseline (0: every CPU the process may use)")
     p.add_argument("--rehearse", action="store_true",
@@ -665,6 +682,30 @@ def xch_stamp_summary(st):
             "gap_us_median": med(gap)}
 
 
+DUMP_WALKERS = 4096   # --dump-outputs: walkers whose trajectory and records are written
+DUMP_BYTES = 48 << 20  # and the cap on what they take (the whole dump stays under 64 MB)
+
+
+def dump_outputs(eng, np, path, horizon, seed):
+    """--dump-outputs: the engine's state as the last timed step left it, i.e. what a caller of
+    rollout + ppo_update reads back: the updated weights and Adam state in full, and the
+    trajectory (states, actions, log-probabilities, rewards, dones, values, returns, advantages)
+    and walker records of a fixed sample of walkers drawn from the seed (all of them when they
+    fit).  Every array is written as float32; the same arguments give the same files."""
+    os.makedirs(path, exist_ok=True)
+    m, v, t = eng.get_adam()
+    state = eng.get_state()
+    per_walker = 4 * (horizon * 25 + state.shape[1])  # 25 trajectory floats per env-step
+    k = max(1, min(eng.n, DUMP_WALKERS, DUMP_BYTES // per_walker))
+    idx = np.sort(np.random.RandomState(seed % (1 << 32)).choice(eng.n, k, replace=False))
+    out = {"weights": eng.get_weights(), "adam_m": m, "adam_v": v, "adam_t": np.array([t]),
+           "walkers": idx, "state": state[idx]}
+    for name, a in eng.get_trajectory(horizon).items():
+        out["trajectory_" + name] = a[:, idx]
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     args = parse()
     json_out = _claim_stdout()
@@ -676,7 +717,7 @@ def main():
         raise SystemExit("--gpus N > 1 must be launched with torch.distributed.run")
     # the CPU leg first, before this process touches the GPU (its workers are spawned)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
 
     import numpy as np
@@ -748,17 +789,22 @@ def main():
     elapsed = time_iterations(eng, args, args.steps, T, upd, barrier)
     prof = eng.profile()
     eng.profile_enable(0)
-    # untimed: one iteration with an event pair around every kernel launch
-    eng.profile_reset()
-    eng.profile_enable(2)
-    time_iterations(eng, args, 1, T, upd)
-    eng.profile_enable(0)
-    prof_k = eng.profile()
-    # untimed: the gradient kernel alone, back to back, timed by one event pair and by a pair
-    # around every launch (their difference: the per-launch event overhead, subtracted from the
-    # level-2 in-update mean for the update roofline)
-    grad_burst_ms = eng.time_gradient(shard.minibatch_local, GRAD_BURST)
-    grad_burst_ev_ms = eng.time_gradient(shard.minibatch_local, GRAD_BURST, per_launch_events=True)
+    # the engine now holds what the last timed step computed; every run below changes it
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, np, args.dump_outputs, T, args.seed)
+    if args.full:
+        # untimed: one iteration with an event pair around every kernel launch
+        eng.profile_reset()
+        eng.profile_enable(2)
+        time_iterations(eng, args, 1, T, upd)
+        eng.profile_enable(0)
+        prof_k = eng.profile()
+        # untimed: the gradient kernel alone, back to back, timed by one event pair and by a pair
+        # around every launch (their difference: the per-launch event overhead, subtracted from
+        # the level-2 in-update mean for the update roofline)
+        grad_burst_ms = eng.time_gradient(shard.minibatch_local, GRAD_BURST)
+        grad_burst_ev_ms = eng.time_gradient(shard.minibatch_local, GRAD_BURST,
+                                             per_launch_events=True)
     # untimed: one iteration with the exchange kernel's per-block clock stamps
     xch_prof = None
     if args.xch_profile and exchange == "ipc":
@@ -771,9 +817,10 @@ def main():
         dist.all_gather_object(xch_prof, mine)
     # untimed: the timed iteration's episode count, then its physics events (counting replay of
     # its actions from the restored state) for the rollout roofline
-    eng.restore()
-    eng.rollout(T)
-    stats = eng.rollout_stats()
+    if args.full:
+        eng.restore()
+        eng.rollout(T)
+        stats = eng.rollout_stats()
 
     t = torch.tensor([elapsed, prof["physics_ms"], prof["update_ms"]], dtype=torch.float64)
     if world > 1:
@@ -782,17 +829,6 @@ def main():
 
     env_steps = world * shard.n_local * T * args.steps
     value = env_steps / elapsed
-    launch_ms = prof["physics_ms"] / max(1, prof["physics_launches"])
-    units = prof["physics_env_steps"] / max(1, prof["physics_launches"])
-    traffic = None
-    if os.path.exists(args.traffic_file):
-        try:
-            tj = json.load(open(args.traffic_file))
-            if tj.get("walkers") == shard.n_local and tj.get("horizon") == T:
-                traffic = tj.get("hbm_bytes_per_launch")
-        except (OSError, ValueError):
-            traffic = None
-    roofline = rollout_roofline(eng, wk, launch_ms, units, T, traffic=traffic)
     out = {
         "metric": METRIC,
         "value": value,
@@ -822,22 +858,32 @@ def main():
         },
         "ppo_update_ms": upd_ms_max / args.steps,
         "rollout_env_steps_per_s": world * shard.n_local * T * args.steps / (phys_ms_max * 1e-3),
-        "regime": {"iterations_before_snapshot": args.regime_iters,
-                   "episodes_per_rollout": int(stats.episodes)},
-        "roofline": roofline,
-        "kernel_ms_one_step": {k: v for k, v in prof_k.items() if k.endswith("_ms")},
-        "roofline_update": update_roofline(prof_k, shard.minibatch_local, shard.n_local, T,
-                                           args.epochs, upd_ms_max / args.steps, grad_burst_ms,
-                                           grad_burst_ev_ms, eng.grad_kernel(shard.minibatch_local),
-                                           exchange),
+        "regime": {"iterations_before_snapshot": args.regime_iters},
     }
+    if args.full:
+        out["regime"]["episodes_per_rollout"] = int(stats.episodes)
+        launch_ms = prof["physics_ms"] / max(1, prof["physics_launches"])
+        units = prof["physics_env_steps"] / max(1, prof["physics_launches"])
+        traffic = None
+        if os.path.exists(args.traffic_file):
+            try:
+                tj = json.load(open(args.traffic_file))
+                if tj.get("walkers") == shard.n_local and tj.get("horizon") == T:
+                    traffic = tj.get("hbm_bytes_per_launch")
+            except (OSError, ValueError):
+                traffic = None
+        out["roofline"] = rollout_roofline(eng, wk, launch_ms, units, T, traffic=traffic)
+        out["kernel_ms_one_step"] = {k: v for k, v in prof_k.items() if k.endswith("_ms")}
+        out["roofline_update"] = update_roofline(
+            prof_k, shard.minibatch_local, shard.n_local, T, args.epochs, upd_ms_max / args.steps,
+            grad_burst_ms, grad_burst_ev_ms, eng.grad_kernel(shard.minibatch_local), exchange)
     if xch_check is not None:
         out["config"]["exchange_check"] = xch_check
     if xch_prof is not None:
         out["xch_profile"] = {"per_rank": xch_prof, "note": xch_stamp_summary.__doc__.split(";")[0]}
-    if world == 1 and not args.rehearse:
+    if args.full and world == 1 and not args.rehearse:
         out["allreduce_1rank"] = allreduce_one_rank(wk, eng, args, T, upd)
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         ex = {}
         ex["config2_physics_4096"] = extra_config(wk, torch, args, 4096, 4096, 4096, T,
                                                   physics_only=True)
@@ -858,7 +904,8 @@ def main():
         out["rehearsal"] = (f"all ranks on one GPU, exchange {exchange}: a check of the "
                             "multi-rank path, not a performance number")
     if rank == 0:
-        detail = write_detail(out, args.detail_file) if args.detail_file else None
+        # a plain run's line holds its whole result: the detail file goes with --full
+        detail = write_detail(out, args.detail_file) if args.full and args.detail_file else None
         print(compact_line(out, detail), file=json_out, flush=True)
     eng.close()
     if world > 1:

@@ -6,6 +6,8 @@ stop_if_fatal() {  # exit codes that mean the GPU step hung, aborted or faulted
   case "$1" in 124|134|137|139) echo "FATAL rc=$1 in $2 -- stopping"; exit "$1";; esac
 }
 STEPS="${STEPS:-tests smoke bench}"
+# the bench step records every figure (CPU baseline, rooflines, other shapes), not only the headline
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 for s in $STEPS; do
   case "$s" in
     tests)

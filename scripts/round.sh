@@ -5,6 +5,8 @@ set -u
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
 R=${ROUND:-r06}
+# the bench and trace steps record every figure (rooflines, other shapes), not only the headline
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 fatal() { case "$1" in 124|134|137|139) echo "FATAL rc=$1 in $2"; exit "$1";; esac; [ "$1" -eq 0 ] || exit "$1"; }
 for s in ${STEPS:-tests smoke bench}; do
   case "$s" in

@@ -8,6 +8,6 @@ for n in ${RANKS:-2 4}; do  # (more ranks than that on ONE GPU: the ranks' spinn
   for x in rccl ipc; do
     port=$((29500 + RANDOM % 1000))
     echo "== ranks=$n exchange=$x"
-    timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $port bench.py --gpus $n --steps 3 --warmup 1 --rehearse --walkers-global $((4096 * n)) --horizon 16 --epochs 2 --regime-iters 1 --exchange $x 2>/dev/null | grep "^{" || exit 1
+    timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $port bench.py --gpus $n --steps 3 --warmup 1 --rehearse --walkers-global $((4096 * n)) --horizon 16 --epochs 2 --regime-iters 1 --exchange $x --full 2>/dev/null | grep "^{" || exit 1
   done
 done

@@ -108,6 +108,23 @@ def test_compact_line_falls_back_to_the_contract_keys():
     assert out["value"] == full["value"]
 
 
+def test_plain_run_is_the_default(monkeypatch):
+    """`--full` (CPU baseline, rooflines, other shapes, detail file) and `--dump-outputs` are off
+    unless asked for; a plain result (headline keys only) makes a valid line"""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs == "" and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+    full = _full()
+    plain = {k: full[k] for k in HEAD + ("ppo_update_ms", "rollout_env_steps_per_s")}
+    out = json.loads(bench.compact_line(plain))
+    for k in HEAD:
+        assert out[k] == plain[k] or k == "config", k
+    assert "roofline" not in out and "cpu_baseline" not in out and "detail_file" not in out
+
+
 def test_xch_stamp_summary():
     """the exchange kernel's per-block stamps (VERDICT r5 #3) -> span / wait / own / gap in us"""
     import numpy as np

@@ -31,7 +31,8 @@ def test_bench_two_rank_rehearsal(exchange):
            "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2",
            "--steps", "2", "--warmup", "1", "--rehearse", "--walkers-global", "4096",
-           "--horizon", "8", "--epochs", "1", "--regime-iters", "1", "--exchange", exchange]
+           "--horizon", "8", "--epochs", "1", "--regime-iters", "1", "--exchange", exchange,
+           "--full"]  # (the rollout roofline names the kernel the shard ran)
     if exchange == "ipc":
         cmd.append("--xch-profile")  # (the exchange kernel's per-block clock split, untimed)
     p = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
