@@ -108,6 +108,16 @@ typedef struct wk_config {
                                leg (SAT axes and contact faces split; for shards of at most
                                one wave per SIMD); 16 = SAT axes over a 16-lane row; 1 = one
                                walker per lane; 0 = auto (4 up to 16,384 walkers, else 2) */
+  int NetworkKernels;       /* 0: the built-in kernels, default network strings only (any other
+                               valid string is WK_ERR_CONFIG); 1: the general kernels, any valid
+                               network string within the limits below, the default strings
+                               included.  Limits (WK_ERR_CONFIG before a device is touched): per
+                               network at most 8 layers (dense and activation together), at
+                               most 4 dense layers, every width in 1..128.  The strings are
+                               copied at wk_create.  One GPU: the multi-GPU gradient exchange
+                               (wk_comm_init, wk_comm_init_host, wk_comm_ipc_handle,
+                               wk_comm_init_ipc) returns WK_ERR_CONFIG on such a context.  Not
+                               part of the JSON document */
 } wk_config;
 
 /* The host-only fields of the reference's JSON configuration (SerializableHyperparameters,
@@ -339,13 +349,30 @@ int wk_load_weights(wk_ctx* ctx, const char* critic_path, const char* actor_path
 int wk_format_weights(const float* params, char* critic_text, size_t critic_cap,
                       char* actor_text, size_t actor_cap);
 int wk_parse_weights(const char* critic_text, const char* actor_text, float* params);
+/* The same for any pair of network strings (NULL: the default string), the vector holding
+ * wk_net_param_count parameters: critic dense layers, then the actor's, each W (out x in,
+ * row-major) then b.  WK_ERR_CONFIG for an invalid or over-limit string, or a text whose
+ * line 0 is another string. */
+int wk_format_weights_net(const char* critic_net, const char* actor_net, const float* params,
+                          char* critic_text, size_t critic_cap, char* actor_text, size_t actor_cap);
+int wk_parse_weights_net(const char* critic_net, const char* actor_net, const char* critic_text,
+                         const char* actor_text, float* params);
+/* Parameter counts of a pair of network strings (NULL: the default string; no GPU), and of a
+ * context's networks: every parameter-shaped argument of a NetworkKernels = 1 context
+ * (wk_get / set_weights, wk_get / set_adam, grads_out) holds n_critic + n_actor floats
+ * instead of WK_NPARAM.  wk_net_param_count returns WK_ERR_CONFIG and a message
+ * (wk_last_error(NULL)) for an invalid string or one beyond the general kernels' limits. */
+int wk_net_param_count(const char* critic_net, const char* actor_net, int* n_critic, int* n_actor);
+int wk_num_params(wk_ctx* ctx, int* n_critic, int* n_actor);
 
 /* Binary checkpoint for bit-exact resume (new; the reference persists only weights):
  * weights, Adam m / v / t, every walker record, Philox step counters, start offsets,
  * materials, running episode rewards / lengths, the episode-log clock and the scene props
  * (descriptions and every walker's prop state; loading replaces the context's scene) (the episode and
  * loss logs are not included: drain them first).  Loading requires the same n_env, seed and EnvOffset; it invalidates the
- * trajectory buffer (roll out again before wk_ppo_update). */
+ * trajectory buffer (roll out again before wk_ppo_update).
+ * A NetworkKernels = 1 context writes a newer file version that also carries its two network
+ * strings; loading a file written with other strings or another NetworkKernels is WK_ERR_ARG. */
 int wk_checkpoint_save(wk_ctx* ctx, const char* path);
 int wk_checkpoint_load(wk_ctx* ctx, const char* path);
 int wk_policy_sample(wk_ctx* ctx, int n, const float* obs /* n*12 */, const int32_t* env_ids,
@@ -503,7 +530,8 @@ int wk_rollout_mapping(wk_ctx* ctx, int* lanes_per_walker, int* walkers_per_wave
  * samples (0 = config Minibatch): 0 producer / consumer waves (k_ppo_grad_ws), 1 tile-parallel
  * teams (k_ppo_grad_tp, two per block), 2 the same with one team per block, 3 one wave per chunk
  * (k_ppo_grad_mfma).  By size (tp1 up to 4,096 samples, tp below 32,768, ws from there) unless
- * WK_GRAD_IMPL = ws / tp / tp1 / mf was set at wk_create. */
+ * WK_GRAD_IMPL = ws / tp / tp1 / mf was set at wk_create.  4: the general networks' kernel
+ * (k_net_grad), on every NetworkKernels = 1 context. */
 int wk_grad_kernel(wk_ctx* ctx, int minibatch);
 
 #ifdef __cplusplus

@@ -36,7 +36,9 @@ public struct WkConfig
     public IntPtr CriticNeuralNetwork, ActorNeuralNetwork;  // NULL = the default networks
     public float DeltaTime;
     public int Horizon, Minibatch, MinibatchGlobal, EnvOffset, RandomizeStart, RandomizeMaterial;
-    public int LanesPerWalker;  // 0 = auto (4-lane split leg pairs up to 16,384 walkers, else the 2-lane leg split; 16-lane rows with RoughFloor)
+    // LanesPerWalker: 0 = auto (4-lane split leg pairs up to 16,384 walkers, else the 2-lane leg split), 1 / 2 / 4 / 16 lanes.
+    // NetworkKernels: 0 = the built-in kernels (default network strings only), 1 = the general kernels (any valid string within the limits)
+    public int LanesPerWalker, NetworkKernels;
 }
 
 // SerializableHyperparameters' host-only fields (Hyperparameters.cs:11-77)
@@ -182,6 +184,11 @@ public static class Wk
     [DllImport(Lib, CharSet = CharSet.Ansi)] public static extern int wk_load_weights(IntPtr ctx, string criticPath, string actorPath);
     [DllImport(Lib)] public static extern int wk_format_weights(float[] p, byte[] critic, UIntPtr criticCap, byte[] actor, UIntPtr actorCap);
     [DllImport(Lib, CharSet = CharSet.Ansi)] public static extern int wk_parse_weights(string critic, string actor, float[] p);
+    // any pair of network strings (a null string = the default one); p holds wk_net_param_count floats
+    [DllImport(Lib, CharSet = CharSet.Ansi)] public static extern int wk_format_weights_net(string criticNet, string actorNet, float[] p, byte[] critic, UIntPtr criticCap, byte[] actor, UIntPtr actorCap);
+    [DllImport(Lib, CharSet = CharSet.Ansi)] public static extern int wk_parse_weights_net(string criticNet, string actorNet, string critic, string actor, float[] p);
+    [DllImport(Lib, CharSet = CharSet.Ansi)] public static extern int wk_net_param_count(string criticNet, string actorNet, out int nCritic, out int nActor);
+    [DllImport(Lib)] public static extern int wk_num_params(IntPtr ctx, out int nCritic, out int nActor);
     [DllImport(Lib, CharSet = CharSet.Ansi)] public static extern int wk_checkpoint_save(IntPtr ctx, string path);
     [DllImport(Lib, CharSet = CharSet.Ansi)] public static extern int wk_checkpoint_load(IntPtr ctx, string path);
 

@@ -112,7 +112,9 @@ NEA_SHAPE(Hexagon, WK_SHAPE_HEXAGON)
 
 namespace Walker {
 namespace PPO {
-// Hyperparameters (Hyperparameters.cs:80-121): static-like defaults as a value type
+// Hyperparameters (Hyperparameters.cs:80-121): static-like defaults as a value type.
+// c.NetworkKernels = 1 with c.CriticNeuralNetwork / c.ActorNeuralNetwork set runs any valid
+// network string on the general kernels (the reference's network menu, ConsoleRenderer.cs:188-189)
 struct Hyperparameters {
   wk_config c;
   Hyperparameters() { wk_config_defaults(&c); }
@@ -174,12 +176,17 @@ class PPOAgent {
     return {cd, ad};
   }
   std::vector<float> Save() {  // NeuralNetwork.Save order (flat)
-    std::vector<float> p(WK_NPARAM);
+    std::vector<float> p(NumParams());
     if (wk_get_weights(ctx_, p.data()) != WK_OK) LogError(wk_last_error(ctx_));
     return p;
   }
+  // parameters of the context's two networks (WK_NPARAM for the default strings)
+  size_t NumParams() const {
+    int nc = 0, na = 0;
+    return wk_num_params(ctx_, &nc, &na) == WK_OK ? (size_t)(nc + na) : (size_t)WK_NPARAM;
+  }
   void Load(const std::vector<float>& p) {
-    if (p.size() != (size_t)WK_NPARAM) { LogError("Loading weights with the wrong size."); return; }
+    if (p.size() != NumParams()) { LogError("Loading weights with the wrong size."); return; }
     if (wk_set_weights(ctx_, p.data()) != WK_OK) LogError(wk_last_error(ctx_));
   }
   // PPOAgent.Save (PPOAgent.cs:192-213): <filePath>Data/Weights/<critic|actor>.weights in

@@ -20,6 +20,7 @@
 #include "../../include/wk_api.h"
 #include "wk_common.h"
 #include "wk_kernels.h"
+#include "wk_net.h"
 #include "wk_text.h"
 
 
@@ -37,6 +38,13 @@ enum ProfKind { PK_PHYS = 0, PK_GRAD, PK_REDUCE, PK_ADAM, PK_ALLRED, PK_RET, PK_
 struct wk_ctx {
   wk_config cfg;
   int grad_impl = -1;  // matrix-core gradient kernel (wk::GI_*; -1 = by minibatch size)
+  // the networks: NetworkKernels = 0 runs the built-in kernels on the default strings, 1 the
+  // general kernels (wk_net.hip) on `net`; np / slabn size every parameter-shaped buffer
+  bool general = false;
+  wk::NetSpec net;
+  wk::NetDesc* net_dev = nullptr;  // device copy {critic, actor}
+  int act_rows = 0;
+  int np = wk::NPARAM, slabn = wk::SLAB;
   int device = 0;
   int n = 0;
   uint64_t seed = 0;
@@ -235,6 +243,7 @@ void wk_config_defaults(wk_config* c) {
   c->EnvOffset = 0;
   c->RandomizeStart = 0;
   c->RandomizeMaterial = 0;
+  c->NetworkKernels = 0;
 }
 
 const char* wk_version(void) { return "wk 0.1 (gfx950)"; }
@@ -260,15 +269,23 @@ static int validate(const wk_config* c, std::string& why) {
   if (c->Lambda <= 0 || c->Lambda > 1) return bad("Invalid lambda value, should be in range 0<x<1");
   if (c->Epsilon <= 0 || c->Epsilon > 1) return bad("Invalid epsilon value, should be in range 0<x<1");
   if (c->LogStandardDeviation <= -5 || c->LogStandardDeviation >= 5) return bad("Invalid log standard deviation value, should be in range -5<x<5");
-  if (c->CriticNeuralNetwork && strcmp(c->CriticNeuralNetwork, kCriticDefault) != 0) {
-    snprintf(b, sizeof(b), "critic network '%s' unsupported: the kernels implement '%s'", c->CriticNeuralNetwork, kCriticDefault);
-    why = b;
-    return WK_ERR_CONFIG;
-  }
-  if (c->ActorNeuralNetwork && strcmp(c->ActorNeuralNetwork, kActorDefault) != 0) {
-    snprintf(b, sizeof(b), "actor network '%s' unsupported: the kernels implement '%s'", c->ActorNeuralNetwork, kActorDefault);
-    why = b;
-    return WK_ERR_CONFIG;
+  if (c->NetworkKernels != 0 && c->NetworkKernels != 1) return bad("NetworkKernels must be 0 (built-in kernels) or 1 (general kernels)");
+  if (c->NetworkKernels == 0) {
+    if (c->CriticNeuralNetwork && strcmp(c->CriticNeuralNetwork, kCriticDefault) != 0) {
+      snprintf(b, sizeof(b), "critic network '%.60s' unsupported: the built-in kernels implement '%s' "
+               "(NetworkKernels = 1 selects the general kernels)", c->CriticNeuralNetwork, kCriticDefault);
+      why = b;
+      return WK_ERR_CONFIG;
+    }
+    if (c->ActorNeuralNetwork && strcmp(c->ActorNeuralNetwork, kActorDefault) != 0) {
+      snprintf(b, sizeof(b), "actor network '%.60s' unsupported: the built-in kernels implement '%s' "
+               "(NetworkKernels = 1 selects the general kernels)", c->ActorNeuralNetwork, kActorDefault);
+      why = b;
+      return WK_ERR_CONFIG;
+    }
+  } else {  // the general kernels: any valid string within wk_net.h's limits
+    wk::NetSpec ns;
+    if (!wk::net_spec(c->CriticNeuralNetwork, c->ActorNeuralNetwork, ns, why)) return WK_ERR_CONFIG;
   }
   if (c->Horizon <= 0) return bad("Horizon must be > 0");
   if (c->Minibatch < 0) return bad("Minibatch must be >= 0");
@@ -297,6 +314,11 @@ static hipError_t rough_order_upload(wk_ctx* c, const float* dx_host) {
   return hipMemcpy(c->order, ord.data(), sizeof(int32_t) * c->n, hipMemcpyHostToDevice);
 }
 
+// W in the matrix-core operand order, for the built-in gradient kernels
+static hipError_t upload_image(wk_ctx* c) {
+  return c->general ? hipSuccess : wk::launch_swizzle(c->W, c->Wz, c->stream);
+}
+
 int wk_create(const wk_config* cfg, int device, int n_env, uint64_t seed, wk_ctx** out) {
   if (!out) { g_create_error = "out is NULL"; return WK_ERR_ARG; }
   *out = nullptr;
@@ -320,8 +342,19 @@ int wk_create(const wk_config* cfg, int device, int n_env, uint64_t seed, wk_ctx
   } restore;
   wk_ctx* x = new wk_ctx();
   x->cfg = c;
-  x->cfg.CriticNeuralNetwork = nullptr;
-  x->cfg.ActorNeuralNetwork = nullptr;
+  // the strings are copied: the caller's pointers are borrowed for this call only
+  x->general = c.NetworkKernels == 1;
+  if (!wk::net_spec(x->general ? c.CriticNeuralNetwork : nullptr, x->general ? c.ActorNeuralNetwork : nullptr,
+                    x->net, why)) {
+    g_create_error = why;
+    delete x;
+    return WK_ERR_CONFIG;
+  }
+  x->cfg.CriticNeuralNetwork = x->net.critic_str.c_str();
+  x->cfg.ActorNeuralNetwork = x->net.actor_str.c_str();
+  x->np = x->net.np;
+  x->slabn = x->general ? wk::net_slab_floats(x->np) : (int)wk::SLAB;
+  x->act_rows = wk::net_act_rows(x->net.critic, x->net.actor);
   if (x->cfg.Minibatch == 0) x->cfg.Minibatch = x->cfg.BatchSize;
   x->device = device;
   x->n = n_env;
@@ -335,7 +368,10 @@ int wk_create(const wk_config* cfg, int device, int n_env, uint64_t seed, wk_ctx
   if (hipSetDevice(device) != hipSuccess) { x->err = "hipSetDevice failed"; return fail(WK_ERR_HIP); }
   // > 64 KiB dynamic LDS for the gradient kernels, set on this device (the attribute is
   // per device; wk_create is the only place, so launches never race on it)
-  if (wk::configure_device_kernels() != hipSuccess) { x->err = "hipFuncSetAttribute failed"; return fail(WK_ERR_HIP); }
+  if (wk::configure_device_kernels() != hipSuccess || wk::configure_net_kernels() != hipSuccess) {
+    x->err = "hipFuncSetAttribute failed";
+    return fail(WK_ERR_HIP);
+  }
   x->grad_impl = wk::grad_impl_env();
   if (hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking) != hipSuccess) {
     x->err = "hipStreamCreate failed";
@@ -386,11 +422,16 @@ int wk_create(const wk_config* cfg, int device, int n_env, uint64_t seed, wk_ctx
   ALLOC(x->dxoff, sizeof(float) * n);
   ALLOC(x->mat, sizeof(int32_t) * n);
   ALLOC(x->rng_t, sizeof(uint32_t) * n);
-  ALLOC(x->W, sizeof(float) * wk::NPARAM);
-  ALLOC(x->Wz, sizeof(float) * wk::mfma_image_floats());
-  ALLOC(x->m, sizeof(float) * wk::NPARAM);
-  ALLOC(x->v, sizeof(float) * wk::NPARAM);
-  ALLOC(x->grad, sizeof(float) * wk::SLAB);
+  const size_t np = (size_t)x->np;
+  ALLOC(x->W, sizeof(float) * np);
+  if (x->general) {  // (no operand-order image: the general kernels read W as it is)
+    ALLOC(x->net_dev, sizeof(wk::NetDesc) * 2);
+  } else {
+    ALLOC(x->Wz, sizeof(float) * wk::mfma_image_floats());
+  }
+  ALLOC(x->m, sizeof(float) * np);
+  ALLOC(x->v, sizeof(float) * np);
+  ALLOC(x->grad, sizeof(float) * x->slabn);
   ALLOC(x->ts, sizeof(float) * 12 * n * T);
   ALLOC(x->ta, sizeof(float) * 4 * n * T);
   ALLOC(x->tlp, sizeof(float) * 4 * n * T);
@@ -440,8 +481,8 @@ int wk_create(const wk_config* cfg, int device, int n_env, uint64_t seed, wk_ctx
   if (hipMemcpy(x->dxoff, dx.data(), sizeof(float) * n, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(x->mat, mt.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemset(x->rng_t, 0, sizeof(uint32_t) * n) != hipSuccess ||
-      hipMemset(x->m, 0, sizeof(float) * wk::NPARAM) != hipSuccess ||
-      hipMemset(x->v, 0, sizeof(float) * wk::NPARAM) != hipSuccess ||
+      hipMemset(x->m, 0, sizeof(float) * np) != hipSuccess ||
+      hipMemset(x->v, 0, sizeof(float) * np) != hipSuccess ||
       hipMemset(x->td, 0, n * T) != hipSuccess ||
       hipMemset(x->ep_acc, 0, sizeof(double) * n) != hipSuccess ||
       hipMemset(x->ep_len, 0, sizeof(int32_t) * n) != hipSuccess ||
@@ -454,9 +495,17 @@ int wk_create(const wk_config* cfg, int device, int n_env, uint64_t seed, wk_ctx
     x->err = "lane order upload failed";
     return fail(WK_ERR_HIP);
   }
+  if (x->general) {
+    const wk::NetDesc nets[2] = {x->net.critic, x->net.actor};
+    if (hipMemcpy(x->net_dev, nets, sizeof nets, hipMemcpyHostToDevice) != hipSuccess) {
+      x->err = "network description upload failed";
+      return fail(WK_ERR_HIP);
+    }
+  }
   if (wk::launch_env_init(P, x->st, x->dxoff, nullptr, 0, x->stream) != hipSuccess ||
-      wk::launch_xavier(x->W, seed, x->stream) != hipSuccess ||
-      wk::launch_swizzle(x->W, x->Wz, x->stream) != hipSuccess ||
+      (x->general ? wk::launch_net_xavier(x->W, seed, x->net_dev, x->np, x->stream)
+                  : wk::launch_xavier(x->W, seed, x->stream)) != hipSuccess ||
+      upload_image(x) != hipSuccess ||
       hipStreamSynchronize(x->stream) != hipSuccess) {
     x->err = "init kernels failed";
     return fail(WK_ERR_HIP);
@@ -480,7 +529,7 @@ int wk_destroy(wk_ctx* c) {
   void* bufs[] = {c->st, c->dxoff, c->mat, c->rng_t, c->W, c->Wz, c->m, c->v, c->grad, c->ts, c->ta,
                   c->tlp, c->tr, c->tv, c->tret, c->tadv, c->td, c->partial, c->scratch, c->scratch2,
                   c->ep_acc, c->ep_len, c->ep_scratch, c->ep_rowcnt, c->ep_count, c->ep_log,
-                  c->loss_log, c->props, c->snap, c->counts, c->order, c->order_cnt, c->pace};
+                  c->loss_log, c->props, c->snap, c->counts, c->order, c->order_cnt, c->pace, c->net_dev};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -563,8 +612,50 @@ static hipError_t launch_physics(wk_ctx* c, int mode, wk::StepArgs& A) {
   return wk::launch_env_step(mode, c->P, A, c->stream);
 }
 
+// The general networks' sampled env-steps (NetworkKernels = 1).  Per env-step: the walkers'
+// observations, the policy kernel on them (Philox step = the walker's env-step counter, as in
+// the fused kernels), then one env-step of the context's own physics kernel in its
+// caller-actions mode -- every mapping, the rough floor, scene props, the lane order and the
+// pacing as they are, and the counters advance as in the fused rollout.  Rows [k][n][.] the
+// caller does not keep (null) go through one scratch row.
+static int net_sampled(wk_ctx* c, int k, float* d_s, float* d_a, float* d_lp, float* d_v, float* d_r,
+                       uint8_t* d_d, float* d_obs, float* d_pos, uint32_t* d_fault) {
+  const size_t n = c->n;
+  float *r_s = nullptr, *r_a = nullptr, *r_lp = nullptr, *r_v = nullptr;
+  if (!d_s || !d_a || !d_lp || !d_v) {
+    if (ensure(c, &c->scratch, &c->scratch_bytes, sizeof(float) * (12 + 4 + 4 + 1) * n)) return WK_ERR_HIP;
+    r_s = (float*)c->scratch;
+    r_a = r_s + 12 * n;
+    r_lp = r_a + 4 * n;
+    r_v = r_lp + 4 * n;
+  }
+  for (int j = 0; j < k; j++) {
+    float* s_row = d_s ? d_s + 12 * n * j : r_s;
+    float* a_row = d_a ? d_a + 4 * n * j : r_a;
+    HIPCHK(c, wk::launch_get_obs(c->P, c->st, s_row, c->stream));
+    HIPCHK(c, wk::launch_net_policy(c->P, c->net_dev, c->act_rows, c->W, c->lp_const, c->n, s_row,
+                                    nullptr, c->rng_t, nullptr, a_row, d_lp ? d_lp + 4 * n * j : r_lp,
+                                    d_v ? d_v + n * j : r_v, c->stream));
+    wk::StepArgs A{};
+    A.st = c->st; A.dxoff = c->dxoff; A.mat = c->mat; A.rng_t = c->rng_t;
+    A.actions = a_row;
+    A.obs_out = d_obs ? d_obs + 12 * n * j : nullptr;
+    A.pos_out = d_pos ? d_pos + 2 * n * j : nullptr;
+    A.rew_out = d_r ? d_r + n * j : nullptr;
+    A.done_out = d_d ? d_d + n * j : nullptr;
+    A.fault_out = d_fault;
+    A.k_steps = 1;
+    HIPCHK(c, launch_physics(c, 0, A));
+  }
+  return WK_OK;
+}
+
 static int step_impl(wk_ctx* c, const float* d_actions, int k, float* d_obs, float* d_rew,
                      uint8_t* d_done, uint32_t* d_fault, int mode, void* trace) {
+  if (c->general && mode >= 2) {
+    ProfScope ps(c, PK_PHYS, (int64_t)k * c->n);
+    return net_sampled(c, k, nullptr, nullptr, nullptr, nullptr, d_rew, d_done, d_obs, nullptr, d_fault);
+  }
   wk::StepArgs A{};
   A.st = c->st; A.dxoff = c->dxoff; A.mat = c->mat; A.rng_t = c->rng_t;
   A.actions = d_actions; A.obs_out = d_obs; A.rew_out = d_rew; A.done_out = d_done;
@@ -713,7 +804,11 @@ int wk_step_sampled(wk_ctx* c, int k, float* states, float* actions, float* logp
   A.t0 = 0; A.k_steps = k;
   {
     ProfScope ps(c, PK_PHYS, (int64_t)kn);
-    HIPCHK(c, launch_physics(c, 3, A));
+    if (c->general) {
+      if (int r = net_sampled(c, k, d_s, d_a, d_lp, d_v, d_r, d_d, A.obs_out, A.pos_out, d_f)) return r;
+    } else {
+      HIPCHK(c, launch_physics(c, 3, A));
+    }
   }
   if (states) HIPCHK(c, hipMemcpyAsync(states, d_s, b12, hipMemcpyDeviceToHost, c->stream));
   if (actions) HIPCHK(c, hipMemcpyAsync(actions, d_a, b4, hipMemcpyDeviceToHost, c->stream));
@@ -1026,15 +1121,15 @@ int wk_get_weights(wk_ctx* c, float* p) {
   DevGuard dg_(c);
   if (!c || !p) return WK_ERR_ARG;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(p, c->W, sizeof(float) * wk::NPARAM, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(p, c->W, sizeof(float) * c->np, hipMemcpyDeviceToHost));
   return WK_OK;
 }
 int wk_set_weights(wk_ctx* c, const float* p) {
   DevGuard dg_(c);
   if (!c || !p) return WK_ERR_ARG;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(c->W, p, sizeof(float) * wk::NPARAM, hipMemcpyHostToDevice));
-  HIPCHK(c, wk::launch_swizzle(c->W, c->Wz, c->stream));
+  HIPCHK(c, hipMemcpy(c->W, p, sizeof(float) * c->np, hipMemcpyHostToDevice));
+  HIPCHK(c, upload_image(c));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return WK_OK;
 }
@@ -1042,8 +1137,8 @@ int wk_get_adam(wk_ctx* c, float* m, float* v, int* t) {
   DevGuard dg_(c);
   if (!c) return WK_ERR_ARG;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (m) HIPCHK(c, hipMemcpy(m, c->m, sizeof(float) * wk::NPARAM, hipMemcpyDeviceToHost));
-  if (v) HIPCHK(c, hipMemcpy(v, c->v, sizeof(float) * wk::NPARAM, hipMemcpyDeviceToHost));
+  if (m) HIPCHK(c, hipMemcpy(m, c->m, sizeof(float) * c->np, hipMemcpyDeviceToHost));
+  if (v) HIPCHK(c, hipMemcpy(v, c->v, sizeof(float) * c->np, hipMemcpyDeviceToHost));
   if (t) *t = c->adam_t;
   return WK_OK;
 }
@@ -1051,8 +1146,8 @@ int wk_set_adam(wk_ctx* c, const float* m, const float* v, int t) {
   DevGuard dg_(c);
   if (!c || t < 0) return WK_ERR_ARG;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (m) HIPCHK(c, hipMemcpy(c->m, m, sizeof(float) * wk::NPARAM, hipMemcpyHostToDevice));
-  if (v) HIPCHK(c, hipMemcpy(c->v, v, sizeof(float) * wk::NPARAM, hipMemcpyHostToDevice));
+  if (m) HIPCHK(c, hipMemcpy(c->m, m, sizeof(float) * c->np, hipMemcpyHostToDevice));
+  if (v) HIPCHK(c, hipMemcpy(c->v, v, sizeof(float) * c->np, hipMemcpyHostToDevice));
   c->adam_t = t;
   return WK_OK;
 }
@@ -1073,9 +1168,15 @@ static int policy_impl(wk_ctx* c, int n, const float* obs, const int32_t* ids, c
   HIPCHK(c, hipMemcpyAsync(d_obs, obs, b_obs, hipMemcpyHostToDevice, c->stream));
   if (ids) HIPCHK(c, hipMemcpyAsync(d_ids, ids, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
   if (steps) HIPCHK(c, hipMemcpyAsync(d_steps, steps, sizeof(uint32_t) * n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, wk::launch_policy(c->P, c->W, c->lp_const, n, d_obs, ids ? d_ids : nullptr,
-                              steps ? d_steps : nullptr, v ? nullptr : d_mean, v ? nullptr : d_act,
-                              v ? nullptr : d_lp, v ? d_v : nullptr, c->stream));
+  if (c->general)
+    HIPCHK(c, wk::launch_net_policy(c->P, c->net_dev, c->act_rows, c->W, c->lp_const, n, d_obs,
+                                    ids ? d_ids : nullptr, steps ? d_steps : nullptr,
+                                    v ? nullptr : d_mean, v ? nullptr : d_act, v ? nullptr : d_lp,
+                                    v ? d_v : nullptr, c->stream));
+  else
+    HIPCHK(c, wk::launch_policy(c->P, c->W, c->lp_const, n, d_obs, ids ? d_ids : nullptr,
+                                steps ? d_steps : nullptr, v ? nullptr : d_mean, v ? nullptr : d_act,
+                                v ? nullptr : d_lp, v ? d_v : nullptr, c->stream));
   if (v) {
     HIPCHK(c, hipMemcpyAsync(v, d_v, b1, hipMemcpyDeviceToHost, c->stream));
   } else {
@@ -1124,7 +1225,12 @@ int wk_rollout(wk_ctx* c, int horizon) {
   A.traj_v = c->tv; A.t0 = 0; A.k_steps = horizon;
   {
     ProfScope ps(c, PK_PHYS, (int64_t)horizon * c->n);
-    HIPCHK(c, launch_physics(c, 3, A));
+    if (c->general) {
+      if (int r = net_sampled(c, horizon, c->ts, c->ta, c->tlp, c->tv, c->tr, c->td, nullptr, nullptr, nullptr))
+        return r;
+    } else {
+      HIPCHK(c, launch_physics(c, 3, A));
+    }
   }
   c->T_valid = horizon;
   if (c->collect) {
@@ -1206,12 +1312,7 @@ static uint64_t* xch_stamp_slot(wk_ctx* c) {
 // one minibatch: gradient kernel -> ordered block reduction -> [RCCL all-reduce] -> Adam
 // wpb == 0: the matrix-core kernel (wk_ppo_mfma.hip); wpb >= 1: the lane-per-neuron
 // kernel (wk_ppo.hip; wpb == 1 visits the samples in minibatch order)
-static int minibatch(wk_ctx* c, wk::GradArgs g, int wpb, int apply_adam) {
-  const int gi = wk::grad_impl_for(c->grad_impl, g.samples);
-  const int nblocks = wpb == 0 ? wk::ppo_grad_mfma_blocks(g.samples, gi)
-                               : (g.samples + wpb * g.spw - 1) / (wpb * g.spw);
-  // block slabs followed by the stage-1 group sums of the ordered reduction
-  const size_t need = ((size_t)nblocks + wk::grad_reduce_groups(nblocks)) * wk::SLAB;
+static int ensure_partial(wk_ctx* c, size_t need) {
   if (c->partial_floats < need) {
     if (c->partial) (void)hipFree(c->partial);
     c->partial = nullptr;
@@ -1219,21 +1320,53 @@ static int minibatch(wk_ctx* c, wk::GradArgs g, int wpb, int apply_adam) {
     HIPCHK(c, hipMalloc((void**)&c->partial, sizeof(float) * need));
     c->partial_floats = need;
   }
+  return WK_OK;
+}
+
+static wk::AdamArgs adam_args(wk_ctx* c) {  // advances the step count
+  wk::AdamArgs a{};
+  c->adam_t += 1;
+  const wk_config& k = c->cfg;
+  a.W = c->W; a.m = c->m; a.v = c->v; a.grad = c->grad; a.Wz = c->Wz;
+  a.c1 = 1.0f - k.Beta1;
+  a.c2 = 1.0f - k.Beta2;
+  a.beta1 = k.Beta1;
+  a.beta2 = k.Beta2;
+  a.bc1 = (float)(1.0 - pow((double)k.Beta1, (double)c->adam_t));
+  a.bc2 = (float)(1.0 - pow((double)k.Beta2, (double)c->adam_t));
+  a.alpha = k.Alpha;
+  a.eps = k.AdamEpsilon;
+  return a;
+}
+
+// the general networks' minibatch: k_net_grad, then the ordered sum of its block slabs with
+// Adam in the same launch (one GPU: the exchanges refuse such a context)
+static int net_minibatch(wk_ctx* c, wk::GradArgs g, int apply_adam) {
+  const int nblocks = wk::net_grad_blocks(g.samples);
+  if (int r = ensure_partial(c, (size_t)nblocks * c->slabn)) return r;
   g.partial = c->partial;
   wk::AdamArgs a{};
-  if (apply_adam) {
-    c->adam_t += 1;
-    const wk_config& k = c->cfg;
-    a.W = c->W; a.m = c->m; a.v = c->v; a.grad = c->grad; a.Wz = c->Wz;
-    a.c1 = 1.0f - k.Beta1;
-    a.c2 = 1.0f - k.Beta2;
-    a.beta1 = k.Beta1;
-    a.beta2 = k.Beta2;
-    a.bc1 = (float)(1.0 - pow((double)k.Beta1, (double)c->adam_t));
-    a.bc2 = (float)(1.0 - pow((double)k.Beta2, (double)c->adam_t));
-    a.alpha = k.Alpha;
-    a.eps = k.AdamEpsilon;
+  if (apply_adam) a = adam_args(c);
+  {
+    ProfScope ps(c, PK_GRAD, 0, 2);
+    HIPCHK(c, wk::launch_net_grad(g, c->net_dev, c->act_rows, c->np, c->stream));
   }
+  ProfScope ps(c, PK_REDUCE, 0, 2);
+  HIPCHK(c, wk::launch_net_reduce(c->partial, nblocks, c->np, c->grad, a, c->stream));
+  return WK_OK;
+}
+
+static int minibatch(wk_ctx* c, wk::GradArgs g, int wpb, int apply_adam) {
+  if (c->general) return net_minibatch(c, g, apply_adam);
+  const int gi = wk::grad_impl_for(c->grad_impl, g.samples);
+  const int nblocks = wpb == 0 ? wk::ppo_grad_mfma_blocks(g.samples, gi)
+                               : (g.samples + wpb * g.spw - 1) / (wpb * g.spw);
+  // block slabs followed by the stage-1 group sums of the ordered reduction
+  const size_t need = ((size_t)nblocks + wk::grad_reduce_groups(nblocks)) * wk::SLAB;
+  if (int r = ensure_partial(c, need)) return r;
+  g.partial = c->partial;
+  wk::AdamArgs a{};
+  if (apply_adam) a = adam_args(c);
   float* part2 = c->partial + (size_t)nblocks * wk::SLAB;
   // with a communicator (any size, also one rank) the collective path runs: reduction,
   // RCCL all-reduce, Adam -- a single-GPU test then covers the multi-GPU sequence
@@ -1354,6 +1487,7 @@ static int ppo_update_impl(wk_ctx* c, const wk_ppo_args* args);
 // roofline; the launches write only the scratch slabs, no weights change)
 int wk_grad_kernel(wk_ctx* c, int minibatch) {
   if (!c || minibatch < 0) return WK_ERR_ARG;
+  if (c->general) return 4;  // k_net_grad
   return wk::grad_impl_for(c->grad_impl, minibatch > 0 ? minibatch : c->cfg.Minibatch);
 }
 
@@ -1410,17 +1544,16 @@ int wk_time_gradient_ex(wk_ctx* c, int minibatch, int reps, int flags, double* m
   g.pk = wk::perm_key(c->seed, 0u, 0u, pool);
   g.base = 0;
   const int gi = wk::grad_impl_for(c->grad_impl, M);
-  const int nblocks = wk::ppo_grad_mfma_blocks(M, gi);
-  const size_t need = ((size_t)nblocks + wk::grad_reduce_groups(nblocks)) * wk::SLAB;
-  if (c->partial_floats < need) {
-    if (c->partial) (void)hipFree(c->partial);
-    c->partial = nullptr;
-    c->partial_floats = 0;
-    HIPCHK(c, hipMalloc((void**)&c->partial, sizeof(float) * need));
-    c->partial_floats = need;
-  }
+  const int nblocks = c->general ? wk::net_grad_blocks(M) : wk::ppo_grad_mfma_blocks(M, gi);
+  const size_t need = c->general ? (size_t)nblocks * c->slabn
+                                 : ((size_t)nblocks + wk::grad_reduce_groups(nblocks)) * wk::SLAB;
+  if (int r = ensure_partial(c, need)) return r;
   g.partial = c->partial;
-  HIPCHK(c, wk::launch_ppo_grad_mfma(g, nblocks, gi, c->stream));  // warm
+  auto launch = [&]() {
+    return c->general ? wk::launch_net_grad(g, c->net_dev, c->act_rows, c->np, c->stream)
+                      : wk::launch_ppo_grad_mfma(g, nblocks, gi, c->stream);
+  };
+  HIPCHK(c, launch());  // warm
   // flags & 1: an event pair around EVERY launch (as profile level 2 times the update's
   // launches), the elapsed times summed -- the burst's per-launch event overhead is the
   // difference to one pair around the whole burst
@@ -1429,7 +1562,7 @@ int wk_time_gradient_ex(wk_ctx* c, int minibatch, int reps, int flags, double* m
   for (auto& e : ev) HIPCHK(c, hipEventCreate(&e));
   for (int i = 0; i < reps; i++) {
     if ((flags & 1) || i == 0) HIPCHK(c, hipEventRecord(ev[2 * ((flags & 1) ? i : 0)], c->stream));
-    HIPCHK(c, wk::launch_ppo_grad_mfma(g, nblocks, gi, c->stream));
+    HIPCHK(c, launch());
     if ((flags & 1) || i == reps - 1) HIPCHK(c, hipEventRecord(ev[2 * ((flags & 1) ? i : 0) + 1], c->stream));
   }
   HIPCHK(c, hipEventSynchronize(ev.back()));
@@ -1459,13 +1592,13 @@ int wk_ppo_update(wk_ctx* c, const wk_ppo_args* args, float* critic_diag, float*
   }
   if (c->collect) {  // the last minibatch's losses, as PPOAgent.Train hands them on (:165-166)
     if (c->loss_count < c->loss_cap)
-      HIPCHK(c, hipMemcpyAsync(c->loss_log + 2 * c->loss_count, c->grad + wk::NPARAM,
+      HIPCHK(c, hipMemcpyAsync(c->loss_log + 2 * c->loss_count, c->grad + c->np,
                                2 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     c->loss_count++;
   }
   if (!critic_diag && !actor_diag) return WK_OK;  // stays asynchronous on the stream
   float diag[3] = {0, 0, 0};
-  HIPCHK(c, hipMemcpyAsync(diag, c->grad + wk::NPARAM, sizeof(diag), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(diag, c->grad + c->np, sizeof(diag), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (critic_diag) *critic_diag = diag[0];
   if (actor_diag) *actor_diag = diag[1];
@@ -1536,15 +1669,15 @@ static int batch_impl(wk_ctx* c, int wpb, int B, float b_div, const float* s, co
   if (r) return r;
   r = minibatch(c, g, wpb, apply_adam);
   if (r) return r;
-  std::vector<float> slab(wk::SLAB);
+  std::vector<float> slab(c->slabn);
   HIPCHK(c, hipMemcpyAsync(slab.data(), c->grad, sizeof(float) * slab.size(), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   r = xch_status(c);  // (IPC: a timed-out exchange left grad stale and applied no Adam)
   if (r) return r;
-  if (grads_out) memcpy(grads_out, slab.data(), sizeof(float) * wk::NPARAM);
-  if (cd) *cd = slab[wk::NPARAM];
-  if (ad) *ad = slab[wk::NPARAM + 1];
-  if (skipped) *skipped = (int)slab[wk::NPARAM + 2];
+  if (grads_out) memcpy(grads_out, slab.data(), sizeof(float) * c->np);
+  if (cd) *cd = slab[c->np];
+  if (ad) *ad = slab[c->np + 1];
+  if (skipped) *skipped = (int)slab[c->np + 2];
   return WK_OK;
 }
 
@@ -1575,6 +1708,10 @@ int wk_comm_unique_id(uint8_t* id) {
 int wk_comm_init(wk_ctx* c, int rank, int nranks, const uint8_t* id) {
   DevGuard dg_(c);
   if (!c || !id || nranks <= 0 || rank < 0 || rank >= nranks) return WK_ERR_ARG;
+  if (c->general) {
+    SETERR(c, "the multi-GPU gradient exchange serves the built-in kernels only (NetworkKernels = 0)");
+    return WK_ERR_CONFIG;
+  }
   if (c->host_ar) { SETERR(c, "the context already has a host all-reduce"); return WK_ERR_STATE; }
   HIPCHK(c, hipSetDevice(c->device));
   ncclUniqueId u;
@@ -1589,6 +1726,10 @@ int wk_comm_init(wk_ctx* c, int rank, int nranks, const uint8_t* id) {
 int wk_comm_init_host(wk_ctx* c, int rank, int nranks, wk_host_allreduce_fn fn, void* user) {
   DevGuard dg_(c);
   if (!c || !fn || nranks <= 0 || rank < 0 || rank >= nranks) return WK_ERR_ARG;
+  if (c->general) {
+    SETERR(c, "the multi-GPU gradient exchange serves the built-in kernels only (NetworkKernels = 0)");
+    return WK_ERR_CONFIG;
+  }
   if (c->comm) { SETERR(c, "the context already has an RCCL communicator"); return WK_ERR_STATE; }
   c->host_ar = fn;
   c->host_ar_user = user;
@@ -1605,6 +1746,10 @@ static_assert(sizeof(hipIpcMemHandle_t) == kIpcDevOff && WK_IPC_HANDLE_BYTES == 
 int wk_comm_ipc_handle(wk_ctx* c, uint8_t* handle) {
   DevGuard dg_(c);
   if (!c || !handle) return WK_ERR_ARG;
+  if (c->general) {
+    SETERR(c, "the multi-GPU gradient exchange serves the built-in kernels only (NetworkKernels = 0)");
+    return WK_ERR_CONFIG;
+  }
   if (!c->xch) {
     // uncached (MTYPE UC) device memory: the peers read it over xGMI and this GPU writes it
     // through no cache; coarse-grained hipMalloc memory is the fallback where the driver cannot
@@ -1637,6 +1782,10 @@ int wk_comm_ipc_handle(wk_ctx* c, uint8_t* handle) {
 int wk_comm_init_ipc(wk_ctx* c, int rank, int nranks, const uint8_t* handles) {
   DevGuard dg_(c);
   if (!c || !handles || nranks <= 0 || rank < 0 || rank >= nranks) return WK_ERR_ARG;
+  if (c->general) {
+    SETERR(c, "the multi-GPU gradient exchange serves the built-in kernels only (NetworkKernels = 0)");
+    return WK_ERR_CONFIG;
+  }
   if (nranks > wk::XCH_MAX_RANKS) { SETERR(c, "the IPC exchange spans at most %d ranks", (int)wk::XCH_MAX_RANKS); return WK_ERR_ARG; }
   if (c->comm || c->host_ar || c->ipc) { SETERR(c, "the context already has an all-reduce"); return WK_ERR_STATE; }
   if (!c->xch) { SETERR(c, "wk_comm_ipc_handle first"); return WK_ERR_STATE; }
@@ -1793,8 +1942,8 @@ int wk_snapshot(wk_ctx* c, int op) {
   struct Seg { void* p; size_t bytes; };
   const Seg segs[] = {
       {c->st, sizeof(float) * wk::NSTATE * n}, {c->rng_t, sizeof(uint32_t) * n},
-      {c->W, sizeof(float) * wk::NPARAM}, {c->Wz, sizeof(float) * wk::mfma_image_floats()},
-      {c->m, sizeof(float) * wk::NPARAM}, {c->v, sizeof(float) * wk::NPARAM},
+      {c->W, sizeof(float) * c->np}, {c->Wz, c->Wz ? sizeof(float) * wk::mfma_image_floats() : 0},
+      {c->m, sizeof(float) * c->np}, {c->v, sizeof(float) * c->np},
       {c->ep_acc, sizeof(double) * n}, {c->ep_len, sizeof(int32_t) * n},
       {c->ep_count, sizeof(uint64_t)},
       {c->props, c->props ? sizeof(float) * n * c->scene.pstride : 0}};
@@ -1880,12 +2029,17 @@ int wk_profile_get(wk_ctx* c, wk_profile* o) {
 
 namespace {
 struct DenseSpec { int off_w, rows, cols, off_b; };
-const DenseSpec kCriticLayers[] = {{wk::OFF_C_W1, 64, 12, wk::OFF_C_B1}, {wk::OFF_C_W2, 1, 64, wk::OFF_C_B2}};
-const DenseSpec kActorLayers[] = {{wk::OFF_A_W1, 64, 12, wk::OFF_A_B1},
-                                  {wk::OFF_A_W2, 64, 64, wk::OFF_A_B2},
-                                  {wk::OFF_A_W3, 4, 64, wk::OFF_A_B3}};
-
-std::string format_network(const float* p, const char* dsl, const DenseSpec* layers, int nl) {
+// the dense layers of a network description, in order
+std::vector<DenseSpec> dense_layers(const wk::NetDesc& d) {
+  std::vector<DenseSpec> v;
+  for (int l = 0; l < d.n_layers; l++)
+    if (d.layer[l].kind == wk::NL_DENSE)
+      v.push_back({d.layer[l].off_w, d.layer[l].out, d.layer[l].in, d.layer[l].off_b});
+  return v;
+}
+std::string format_network(const float* p, const char* dsl, const wk::NetDesc& net) {
+  const std::vector<DenseSpec> layers = dense_layers(net);
+  const int nl = (int)layers.size();
   std::string text = std::string(dsl) + "\n";
   for (int l = 0; l < nl; l++) {
     const DenseSpec& d = layers[l];
@@ -1900,8 +2054,10 @@ std::string format_network(const float* p, const char* dsl, const DenseSpec* lay
 
 // NeuralNetwork.Load / ValidateWeights / DenseLayer.Load semantics: the DSL line must
 // match, every token must parse, and each layer needs rows*cols weights then rows biases.
-int parse_network(const char* text, const char* dsl, const DenseSpec* layers, int nl, float* p,
+int parse_network(const char* text, const char* dsl, const wk::NetDesc& net, float* p,
                   std::string& why) {
+  const std::vector<DenseSpec> layers = dense_layers(net);
+  const int nl = (int)layers.size();
   std::vector<std::string> lines;
   std::string cur;
   for (const char* q = text; *q; q++) {
@@ -1975,8 +2131,12 @@ struct CkptExt {
 static_assert(sizeof(CkptExt) == 16, "checkpoint extension");
 // 3: + scene section (int32 n_props, wk_prop[n_props], [n][pstride]); 4: + CkptExt
 const uint32_t kCkptVersion = 4;
-size_t ckpt_bytes(size_t n) {
-  return sizeof(CkptHeader) + sizeof(float) * (3 * wk::NPARAM + n * wk::NSTATE + 2 * n) +
+// 5: a general-network context (NetworkKernels = 1; CkptExt.reserved0 = 1): after CkptExt two
+// uint32 lengths and the critic and actor strings, and nparam parameters of that network.  A
+// built-in context still writes version 4, byte for byte as before
+const uint32_t kCkptVersionNet = 5;
+size_t ckpt_bytes(size_t n, size_t np) {
+  return sizeof(CkptHeader) + sizeof(float) * (3 * np + n * wk::NSTATE + 2 * n) +
          sizeof(int32_t) * n + sizeof(double) * n + sizeof(int32_t) * n;
 }
 }  // namespace
@@ -1985,9 +2145,37 @@ extern "C" {
 
 int wk_format_weights(const float* params, char* critic, size_t critic_cap, char* actor,
                       size_t actor_cap) {
+  return wk_format_weights_net(nullptr, nullptr, params, critic, critic_cap, actor, actor_cap);
+}
+
+int wk_parse_weights(const char* critic, const char* actor, float* params) {
+  return wk_parse_weights_net(nullptr, nullptr, critic, actor, params);
+}
+
+int wk_net_param_count(const char* critic, const char* actor, int* n_critic, int* n_actor) {
+  wk::NetSpec ns;
+  std::string why;
+  if (!wk::net_spec(critic, actor, ns, why)) { g_create_error = why; return WK_ERR_CONFIG; }
+  if (n_critic) *n_critic = ns.critic.n_params;
+  if (n_actor) *n_actor = ns.actor.n_params;
+  return WK_OK;
+}
+
+int wk_num_params(wk_ctx* c, int* n_critic, int* n_actor) {
+  if (!c) return WK_ERR_ARG;
+  if (n_critic) *n_critic = c->net.critic.n_params;
+  if (n_actor) *n_actor = c->net.actor.n_params;
+  return WK_OK;
+}
+
+int wk_format_weights_net(const char* critic_net, const char* actor_net, const float* params,
+                          char* critic, size_t critic_cap, char* actor, size_t actor_cap) {
   if (!params) return WK_ERR_ARG;
-  const std::string c = format_network(params, kCriticDefault, kCriticLayers, 2);
-  const std::string a = format_network(params, kActorDefault, kActorLayers, 3);
+  wk::NetSpec ns;
+  std::string why;
+  if (!wk::net_spec(critic_net, actor_net, ns, why)) { g_create_error = why; return WK_ERR_CONFIG; }
+  const std::string c = format_network(params, ns.critic_str.c_str(), ns.critic);
+  const std::string a = format_network(params, ns.actor_str.c_str(), ns.actor);
   if (!critic || !actor || critic_cap < c.size() + 1 || actor_cap < a.size() + 1)
     return -(int)(c.size() > a.size() ? c.size() + 1 : a.size() + 1);  // needed capacity
   memcpy(critic, c.c_str(), c.size() + 1);
@@ -1995,25 +2183,28 @@ int wk_format_weights(const float* params, char* critic, size_t critic_cap, char
   return WK_OK;
 }
 
-int wk_parse_weights(const char* critic, const char* actor, float* params) {
+int wk_parse_weights_net(const char* critic_net, const char* actor_net, const char* critic,
+                         const char* actor, float* params) {
   if (!critic || !actor || !params) { g_create_error = "null argument"; return WK_ERR_ARG; }
-  std::vector<float> p(wk::NPARAM, 0.0f);
+  wk::NetSpec ns;
   std::string why;
-  int r = parse_network(critic, kCriticDefault, kCriticLayers, 2, p.data(), why);
-  if (r == WK_OK) r = parse_network(actor, kActorDefault, kActorLayers, 3, p.data(), why);
+  if (!wk::net_spec(critic_net, actor_net, ns, why)) { g_create_error = why; return WK_ERR_CONFIG; }
+  std::vector<float> p(ns.np, 0.0f);
+  int r = parse_network(critic, ns.critic_str.c_str(), ns.critic, p.data(), why);
+  if (r == WK_OK) r = parse_network(actor, ns.actor_str.c_str(), ns.actor, p.data(), why);
   if (r != WK_OK) { g_create_error = why; return r; }
-  memcpy(params, p.data(), sizeof(float) * wk::NPARAM);
+  memcpy(params, p.data(), sizeof(float) * ns.np);
   return WK_OK;
 }
 
 int wk_save_weights(wk_ctx* c, const char* critic_path, const char* actor_path) {
   DevGuard dg_(c);
   if (!c || !critic_path || !actor_path) return WK_ERR_ARG;
-  std::vector<float> p(wk::NPARAM);
+  std::vector<float> p(c->np);
   int r = wk_get_weights(c, p.data());
   if (r) return r;
-  const std::string ct = format_network(p.data(), kCriticDefault, kCriticLayers, 2);
-  const std::string at = format_network(p.data(), kActorDefault, kActorLayers, 3);
+  const std::string ct = format_network(p.data(), c->net.critic_str.c_str(), c->net.critic);
+  const std::string at = format_network(p.data(), c->net.actor_str.c_str(), c->net.actor);
   if (!write_file(critic_path, ct.data(), ct.size()) || !write_file(actor_path, at.data(), at.size())) {
     SETERR(c, "cannot write weights files '%s' / '%s'", critic_path, actor_path);
     return WK_ERR_ARG;
@@ -2029,12 +2220,18 @@ int wk_load_weights(wk_ctx* c, const char* critic_path, const char* actor_path) 
     SETERR(c, "cannot read weights files '%s' / '%s'", critic_path, actor_path);
     return WK_ERR_ARG;
   }
-  std::vector<float> p(wk::NPARAM, 0.0f);
+  std::vector<float> p(c->np, 0.0f);
   std::string why;
-  int r = parse_network(ct.c_str(), kCriticDefault, kCriticLayers, 2, p.data(), why);
-  if (r == WK_OK) r = parse_network(at.c_str(), kActorDefault, kActorLayers, 3, p.data(), why);
+  int r = parse_network(ct.c_str(), c->net.critic_str.c_str(), c->net.critic, p.data(), why);
+  if (r == WK_OK) r = parse_network(at.c_str(), c->net.actor_str.c_str(), c->net.actor, p.data(), why);
   if (r != WK_OK) { c->err = why; return r; }
   return wk_set_weights(c, p.data());
+}
+
+// a version-5 file's network section: two uint32 lengths, then the critic and actor strings
+static std::string net_section(const wk_ctx* c) {
+  const uint32_t len[2] = {(uint32_t)c->net.critic_str.size(), (uint32_t)c->net.actor_str.size()};
+  return std::string((const char*)len, sizeof len) + c->net.critic_str + c->net.actor_str;
 }
 
 // Binary checkpoint for exact resume: weights, Adam m / v / t, every walker record,
@@ -2043,20 +2240,23 @@ int wk_checkpoint_save(wk_ctx* c, const char* path) {
   DevGuard dg_(c);
   if (!c || !path) return WK_ERR_ARG;
   const size_t n = c->n;
-  CkptHeader h{kCkptMagic, kCkptVersion, (uint32_t)n, (uint32_t)wk::NSTATE, (uint32_t)wk::NPARAM,
-               (uint32_t)c->adam_t, c->seed, c->cfg.EnvOffset, c->cfg.Iterations,
+  const size_t wbytes = sizeof(float) * c->np;
+  CkptHeader h{kCkptMagic, c->general ? kCkptVersionNet : kCkptVersion, (uint32_t)n, (uint32_t)wk::NSTATE,
+               (uint32_t)c->np, (uint32_t)c->adam_t, c->seed, c->cfg.EnvOffset, c->cfg.Iterations,
                c->cfg.MaxTimesteps, c->rollout_steps};
   const int np = c->scene.n_props;
   const size_t scene_bytes = sizeof(int32_t) + sizeof(wk_prop) * np + sizeof(float) * n * c->scene.pstride;
-  const CkptExt ext{c->cfg.RoughFloor, c->P.lanes, 0, 0};
-  std::vector<char> buf(ckpt_bytes(n) + sizeof ext + scene_bytes);
+  const CkptExt ext{c->cfg.RoughFloor, c->P.lanes, c->general ? 1 : 0, 0};
+  const std::string nets = c->general ? net_section(c) : std::string();
+  std::vector<char> buf(ckpt_bytes(n, c->np) + sizeof ext + nets.size() + scene_bytes);
   char* q = buf.data();
   memcpy(q, &h, sizeof h); q += sizeof h;
   memcpy(q, &ext, sizeof ext); q += sizeof ext;
+  memcpy(q, nets.data(), nets.size()); q += nets.size();
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(q, c->W, sizeof(float) * wk::NPARAM, hipMemcpyDeviceToHost)); q += sizeof(float) * wk::NPARAM;
-  HIPCHK(c, hipMemcpy(q, c->m, sizeof(float) * wk::NPARAM, hipMemcpyDeviceToHost)); q += sizeof(float) * wk::NPARAM;
-  HIPCHK(c, hipMemcpy(q, c->v, sizeof(float) * wk::NPARAM, hipMemcpyDeviceToHost)); q += sizeof(float) * wk::NPARAM;
+  HIPCHK(c, hipMemcpy(q, c->W, wbytes, hipMemcpyDeviceToHost)); q += wbytes;
+  HIPCHK(c, hipMemcpy(q, c->m, wbytes, hipMemcpyDeviceToHost)); q += wbytes;
+  HIPCHK(c, hipMemcpy(q, c->v, wbytes, hipMemcpyDeviceToHost)); q += wbytes;
   HIPCHK(c, hipMemcpy(q, c->st, sizeof(float) * n * wk::NSTATE, hipMemcpyDeviceToHost)); q += sizeof(float) * n * wk::NSTATE;
   HIPCHK(c, hipMemcpy(q, c->rng_t, sizeof(uint32_t) * n, hipMemcpyDeviceToHost)); q += sizeof(uint32_t) * n;
   HIPCHK(c, hipMemcpy(q, c->dxoff, sizeof(float) * n, hipMemcpyDeviceToHost)); q += sizeof(float) * n;
@@ -2085,7 +2285,7 @@ int wk_checkpoint_load(wk_ctx* c, const char* path) {
   CkptHeader h;
   if (data.size() < sizeof h) { SETERR(c, "checkpoint '%s' truncated", path); return WK_ERR_ARG; }
   memcpy(&h, data.data(), sizeof h);
-  if (h.magic != kCkptMagic || h.version < 2 || h.version > kCkptVersion) {
+  if (h.magic != kCkptMagic || h.version < 2 || h.version > kCkptVersionNet) {
     SETERR(c, "'%s' is not a wk checkpoint", path);
     return WK_ERR_ARG;
   }
@@ -2098,10 +2298,29 @@ int wk_checkpoint_load(wk_ctx* c, const char* path) {
               "before version 4, so it cannot be resumed safely", path, h.version);
     return WK_ERR_CONFIG;
   }
-  const size_t ext_bytes = sizeof(CkptExt);
+  size_t ext_bytes = sizeof(CkptExt);
   CkptExt ext{0, 0, 0, 0};
   if (data.size() >= sizeof h + ext_bytes) memcpy(&ext, data.data() + sizeof h, sizeof ext);
-  size_t need = ckpt_bytes(n) + ext_bytes + sizeof(int32_t);
+  // the networks first: a file of other networks (or of the other kind of kernels) has another
+  // parameter count and layout
+  const bool file_general = h.version >= kCkptVersionNet;
+  if (file_general != c->general || (ext.reserved0 != 0) != c->general) {
+    SETERR(c, "checkpoint '%s' was written with NetworkKernels %d (context: %d)", path,
+           file_general ? 1 : 0, c->general ? 1 : 0);
+    return WK_ERR_ARG;
+  }
+  if (file_general) {
+    const std::string mine = net_section(c);
+    if (data.size() < sizeof h + ext_bytes + mine.size() ||
+        memcmp(data.data() + sizeof h + ext_bytes, mine.data(), mine.size()) != 0) {
+      SETERR(c, "checkpoint '%s' was written for other networks than this context's '%s' / '%s'", path,
+             c->net.critic_str.c_str(), c->net.actor_str.c_str());
+      return WK_ERR_ARG;
+    }
+    ext_bytes += mine.size();
+  }
+  const size_t wbytes = sizeof(float) * c->np;
+  size_t need = ckpt_bytes(n, c->np) + ext_bytes + sizeof(int32_t);
   int32_t np = 0;
   std::vector<wk_prop> desc;
   if (data.size() >= need) {
@@ -2120,7 +2339,7 @@ int wk_checkpoint_load(wk_ctx* c, const char* path) {
       need += sizeof(float) * n * pstride;
     }
   }
-  if (h.n_env != n || h.nstate != (uint32_t)wk::NSTATE || h.nparam != (uint32_t)wk::NPARAM || data.size() != need) {
+  if (h.n_env != n || h.nstate != (uint32_t)wk::NSTATE || h.nparam != (uint32_t)c->np || data.size() != need) {
     SETERR(c, "checkpoint '%s' is for %u walkers (context has %zu)", path, h.n_env, n);
     return WK_ERR_ARG;
   }
@@ -2143,7 +2362,7 @@ int wk_checkpoint_load(wk_ctx* c, const char* path) {
   }
   {  // the walker records keep rigid template poles, checked before any write
     std::vector<float> rec(n * wk::NSTATE);
-    memcpy(rec.data(), data.data() + sizeof h + ext_bytes + sizeof(float) * 3 * wk::NPARAM,
+    memcpy(rec.data(), data.data() + sizeof h + ext_bytes + 3 * wbytes,
            sizeof(float) * rec.size());
     if (int r = check_state_or_fail(c, rec.data())) return r;
   }
@@ -2152,9 +2371,9 @@ int wk_checkpoint_load(wk_ctx* c, const char* path) {
   if (int r = wk_set_scene(c, desc.data(), (int)desc.size()); r != WK_OK) return r;
   const char* q = data.data() + sizeof h + ext_bytes;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(c->W, q, sizeof(float) * wk::NPARAM, hipMemcpyHostToDevice)); q += sizeof(float) * wk::NPARAM;
-  HIPCHK(c, hipMemcpy(c->m, q, sizeof(float) * wk::NPARAM, hipMemcpyHostToDevice)); q += sizeof(float) * wk::NPARAM;
-  HIPCHK(c, hipMemcpy(c->v, q, sizeof(float) * wk::NPARAM, hipMemcpyHostToDevice)); q += sizeof(float) * wk::NPARAM;
+  HIPCHK(c, hipMemcpy(c->W, q, wbytes, hipMemcpyHostToDevice)); q += wbytes;
+  HIPCHK(c, hipMemcpy(c->m, q, wbytes, hipMemcpyHostToDevice)); q += wbytes;
+  HIPCHK(c, hipMemcpy(c->v, q, wbytes, hipMemcpyHostToDevice)); q += wbytes;
   HIPCHK(c, hipMemcpy(c->st, q, sizeof(float) * n * wk::NSTATE, hipMemcpyHostToDevice)); q += sizeof(float) * n * wk::NSTATE;
   HIPCHK(c, hipMemcpy(c->rng_t, q, sizeof(uint32_t) * n, hipMemcpyHostToDevice)); q += sizeof(uint32_t) * n;
   HIPCHK(c, hipMemcpy(c->dxoff, q, sizeof(float) * n, hipMemcpyHostToDevice));
@@ -2175,7 +2394,7 @@ int wk_checkpoint_load(wk_ctx* c, const char* path) {
   c->rollout_steps = h.rollout_steps;
   c->T_valid = 0;
   c->returns_valid = 0;
-  HIPCHK(c, wk::launch_swizzle(c->W, c->Wz, c->stream));
+  HIPCHK(c, upload_image(c));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return WK_OK;
 }

@@ -26,6 +26,7 @@
 #include <string>
 
 #include "../../include/wk_api.h"
+#include "wk_net.h"
 #include "wk_text.h"
 
 namespace {
@@ -60,22 +61,9 @@ bool valid_file_path(const char* s) {
   return s[n - 1] == '/' && stat(s, &st) == 0 && S_ISDIR(st.st_mode);
 }
 
-// ConsoleRenderer.ValidateNeuralNetwork (:661-682)
-bool valid_network(const char* s, bool critic, std::string& why) {
-  if (!s) { why = "neural network not valid, check syntax"; return false; }
-  static const std::regex pat("^Input ((\\|[1-9][0-9]*\\| )|(\\((LeakyReLU|TanH|ReLU)\\) ))+Output$");
-  if (!std::regex_match(s, pat)) { why = "neural network not valid, check syntax"; return false; }
-  const std::string t(s);
-  const size_t b = t.rfind('|'), a = t.rfind('|', b - 1);
-  const long out = strtol(t.substr(a + 1, b - a - 1).c_str(), nullptr, 10);
-  const long need = critic ? 1 : 4;
-  if (out != need) {
-    why = "last dense layer should output " + std::to_string(need) + ", currently outputs " +
-          std::to_string(out);
-    return false;
-  }
-  return true;
-}
+// ConsoleRenderer.ValidateNeuralNetwork (:661-682): wk_net.h, shared with the general kernels'
+// network description
+using wk::valid_network;
 
 // System.Text.Json number conversions (Utf8JsonReader.TryGetInt32 / TryGetSingle)
 bool get_int(const wk::JsonValue& v, int& out) {

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "wk_common.h"
+#include "wk_net.h"
 
 namespace wk {
 
@@ -188,6 +189,22 @@ size_t xch_region_bytes();
 hipError_t launch_reduce_xch_adam(const XchArgs& x, hipStream_t s);
 hipError_t launch_normalize(float* x, int n, float eps, hipStream_t s);
 hipError_t launch_xavier(float* W, uint64_t seed, hipStream_t s);
+
+// the general networks' kernels (wk_net.hip; NetworkKernels = 1).  nets: device copy of
+// {critic, actor}; act_rows: net_act_rows of the two
+enum : int { NET_MAX_BLOCKS = 1024 };  // gradient blocks (one slab each) per minibatch
+hipError_t configure_net_kernels();
+int net_act_rows(const NetDesc& critic, const NetDesc& actor);
+int net_slab_floats(int np);
+int net_grad_blocks(int samples);
+hipError_t launch_net_policy(const EnvParams& P, const NetDesc* nets, int act_rows, const float* W,
+                             float lp_const, int n, const float* obs, const int32_t* env_ids,
+                             const uint32_t* steps, float* mean, float* act, float* logp, float* v,
+                             hipStream_t s);
+hipError_t launch_net_grad(const GradArgs& g, const NetDesc* nets, int act_rows, int np, hipStream_t s);
+hipError_t launch_net_reduce(const float* partial, int nblocks, int np, float* grad, const AdamArgs& a,
+                             hipStream_t s);
+hipError_t launch_net_xavier(float* W, uint64_t seed, const NetDesc* nets, int np, hipStream_t s);
 
 // data collection: per-episode totals of a recorded rollout appended to the device log;
 // layout == wk_episode_rec (include/wk_api.h)

@@ -20,6 +20,7 @@
 #include "wk_kernels.h"
 #include "wk_mfma_layout.h"
 #include "wk_region_prof.h"
+#include "wk_sample.h"
 
 // Build parts (the Makefile compiles this file eight times, in parallel): kernels are
 // templates instantiated where the host shims at the end launch them, so each part holds the
@@ -551,29 +552,6 @@ DEV float critic_value(const float* __restrict__ W, const float s[12]) {
     v = v + W[OFF_C_W2 + j] * h;
   }
   return v + W[OFF_C_B2];
-}
-
-// NormalDistribution.BoxMullerTransform (NormalDistribution.cs:12-19) with Philox draws
-DEV void sample_actions(const EnvParams& P, float lp_const, uint32_t gid, uint32_t t,
-                        const float mean[4], float act[4], float logp[4]) {
-  const float PI_F = 3.14159265358979323846f;
-#pragma unroll
-  for (int d = 0; d < 4; d++) {
-    U4 o = philox(P.seed, gid, t, (uint32_t)d, ST_ACT);
-    float u1 = next_double_f(o.x, o.y);
-    float u2 = next_double_f(o.z, o.w);
-    if (u1 == 0.0f) u1 = 1.0f;
-    float z = sqrtf(-2.0f * logf(u1)) * sinf(2.0f * PI_F * u2);
-    act[d] = mean[d] + (P.std_ * z);
-  }
-#pragma unroll
-  for (int d = 0; d < 4; d++) {
-    // LogProbabilityDensity (:24-32); lp_const = -ln(std) - ln(sqrt(2 pi)) (host libm)
-    float fraction = (act[d] - mean[d]) / P.std_;
-    fraction *= fraction;
-    fraction /= 2.0f;
-    logp[d] = lp_const - fraction;
-  }
 }
 
 // Row-parallel policy for L = 16 lanes per walker: lane `sub` owns neurons 4*sub..4*sub+3

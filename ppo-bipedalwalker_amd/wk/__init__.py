@@ -45,6 +45,7 @@ EXPORTS = [
     "wk_comm_ipc_handle", "wk_comm_init_ipc", "wk_comm_info", "wk_comm_set_timeout",
     "wk_comm_xch_profile", "wk_comm_xch_stamps", "wk_check_state", "wk_take_actions",
     "wk_object_update", "wk_joint_step", "wk_body_order",
+    "wk_net_param_count", "wk_num_params", "wk_format_weights_net", "wk_parse_weights_net",
 ]
 
 
@@ -70,7 +71,7 @@ class WkConfig(C.Structure):
         ("ActorNeuralNetwork", C.c_char_p), ("DeltaTime", C.c_float), ("Horizon", C.c_int),
         ("Minibatch", C.c_int), ("MinibatchGlobal", C.c_int), ("EnvOffset", C.c_int),
         ("RandomizeStart", C.c_int), ("RandomizeMaterial", C.c_int),
-        ("LanesPerWalker", C.c_int),
+        ("LanesPerWalker", C.c_int), ("NetworkKernels", C.c_int),
     ]
 
 
@@ -268,6 +269,11 @@ def load_library(path=None):
         "wk_profile_reset": (I, [P]),
         "wk_count_events": (I, [P, I, P]),
         "wk_snapshot": (I, [P, I]),
+        "wk_net_param_count": (I, [C.c_char_p, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "wk_num_params": (I, [P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "wk_format_weights_net": (I, [C.c_char_p, C.c_char_p, P, C.c_char_p, C.c_size_t, C.c_char_p,
+                                      C.c_size_t]),
+        "wk_parse_weights_net": (I, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -357,26 +363,45 @@ def write_data_file(path, total_rewards, critic_losses, actor_losses):
         raise WkError(f"wk_write_data_file failed ({rc}): {lib.wk_last_error(None).decode()}")
 
 
-def format_weights(params):
-    """(critic_text, actor_text) of a WK_NPARAM vector in the reference's weights-file format
-    (NeuralNetwork.Save NeuralNetwork.cs:159-176; one line per entry, newline-terminated)."""
+def _net(s):
+    return None if s is None else (s if isinstance(s, bytes) else s.encode())
+
+
+def net_param_count(critic=None, actor=None):
+    """wk_net_param_count: (critic, actor) parameter counts of two network strings (None: the
+    default string); WkError for an invalid string or one beyond the general kernels' limits."""
     lib = load_library()
-    p = _f32(params, (NPARAM,))
-    need = -lib.wk_format_weights(_ptr(p), None, 0, None, 0)
-    if need <= 0:
-        raise WkError("wk_format_weights: size query failed")
-    cb, ab = C.create_string_buffer(need), C.create_string_buffer(need)
-    rc = lib.wk_format_weights(_ptr(p), cb, need, ab, need)
+    nc, na = C.c_int(), C.c_int()
+    rc = lib.wk_net_param_count(_net(critic), _net(actor), C.byref(nc), C.byref(na))
     if rc != 0:
-        raise WkError(f"wk_format_weights failed ({rc})")
+        raise WkError(f"wk_net_param_count failed ({rc}): {lib.wk_last_error(None).decode()}")
+    return nc.value, na.value
+
+
+def format_weights(params, critic=None, actor=None):
+    """(critic_text, actor_text) of a parameter vector in the reference's weights-file format
+    (NeuralNetwork.Save NeuralNetwork.cs:159-176; one line per entry, newline-terminated);
+    critic / actor: the network strings (None: the default ones, a WK_NPARAM vector)."""
+    lib = load_library()
+    p = _f32(params, (sum(net_param_count(critic, actor)),))
+    cn, an = _net(critic), _net(actor)
+    need = -lib.wk_format_weights_net(cn, an, _ptr(p), None, 0, None, 0)
+    if need <= 0:
+        raise WkError("wk_format_weights_net: size query failed")
+    cb, ab = C.create_string_buffer(need), C.create_string_buffer(need)
+    rc = lib.wk_format_weights_net(cn, an, _ptr(p), cb, need, ab, need)
+    if rc != 0:
+        raise WkError(f"wk_format_weights_net failed ({rc})")
     return cb.value.decode(), ab.value.decode()
 
 
-def parse_weights(critic_text, actor_text):
-    """WK_NPARAM vector from weights-file texts (NeuralNetwork.Load NeuralNetwork.cs:94-115)."""
+def parse_weights(critic_text, actor_text, critic=None, actor=None):
+    """parameter vector from weights-file texts (NeuralNetwork.Load NeuralNetwork.cs:94-115) of
+    the networks critic / actor (None: the default strings, WK_NPARAM values)."""
     lib = load_library()
-    p = np.empty(NPARAM, np.float32)
-    rc = lib.wk_parse_weights(critic_text.encode(), actor_text.encode(), _ptr(p))
+    p = np.empty(sum(net_param_count(critic, actor)), np.float32)
+    rc = lib.wk_parse_weights_net(_net(critic), _net(actor), critic_text.encode(), actor_text.encode(),
+                                  _ptr(p))
     if rc != 0:
         raise WkError(f"wk_parse_weights failed ({rc}): {lib.wk_last_error(None).decode()}")
     return p
@@ -395,6 +420,9 @@ class Engine:
         if rc != 0:
             raise WkError(f"wk_create failed ({rc}): {self.lib.wk_last_error(None).decode()}")
         self.h = h
+        nc, na = C.c_int(), C.c_int()
+        self._chk(self.lib.wk_num_params(self.h, C.byref(nc), C.byref(na)), "wk_num_params")
+        self.nparam_critic, self.nparam = nc.value, nc.value + na.value
 
     # -- plumbing --
     def _chk(self, rc, what):
@@ -511,24 +539,24 @@ class Engine:
 
     # -- policy --
     def get_weights(self):
-        p = np.empty(NPARAM, np.float32)
+        p = np.empty(self.nparam, np.float32)
         self._chk(self.lib.wk_get_weights(self.h, _ptr(p)), "wk_get_weights")
         return p
 
     def set_weights(self, p):
-        p = _f32(p, (NPARAM,))
+        p = _f32(p, (self.nparam,))
         self._chk(self.lib.wk_set_weights(self.h, _ptr(p)), "wk_set_weights")
 
     def get_adam(self):
-        m = np.empty(NPARAM, np.float32)
-        v = np.empty(NPARAM, np.float32)
+        m = np.empty(self.nparam, np.float32)
+        v = np.empty(self.nparam, np.float32)
         t = C.c_int()
         self._chk(self.lib.wk_get_adam(self.h, _ptr(m), _ptr(v), C.byref(t)), "wk_get_adam")
         return m, v, t.value
 
     def set_adam(self, m, v, t):
-        m = _f32(m, (NPARAM,))
-        v = _f32(v, (NPARAM,))
+        m = _f32(m, (self.nparam,))
+        v = _f32(v, (self.nparam,))
         self._chk(self.lib.wk_set_adam(self.h, _ptr(m), _ptr(v), int(t)), "wk_set_adam")
 
     def save_weights(self, critic_path, actor_path):
@@ -646,7 +674,7 @@ class Engine:
     def train_batch(self, states, actions, logp_old, returns, adv, b_div=None, apply_adam=True):
         s, a, l, r, v = (_f32(states), _f32(actions), _f32(logp_old), _f32(returns), _f32(adv))
         B = r.shape[0]
-        grads = np.empty(NPARAM, np.float32)
+        grads = np.empty(self.nparam, np.float32)
         cd, ad, sk = C.c_float(), C.c_float(), C.c_int()
         self._chk(self.lib.wk_train_batch(
             self.h, int(B), float(B if b_div is None else b_div), _ptr(s), _ptr(a), _ptr(l),
@@ -658,7 +686,7 @@ class Engine:
         """The matrix-core minibatch gradient wk_ppo_update applies (no Adam)."""
         s, a, l, r, v = (_f32(states), _f32(actions), _f32(logp_old), _f32(returns), _f32(adv))
         B = r.shape[0]
-        grads = np.empty(NPARAM, np.float32)
+        grads = np.empty(self.nparam, np.float32)
         cd, ad, sk = C.c_float(), C.c_float(), C.c_int()
         self._chk(self.lib.wk_minibatch_gradient(
             self.h, int(B), float(B if b_div is None else b_div), _ptr(s), _ptr(a), _ptr(l),
@@ -789,7 +817,7 @@ class Engine:
         return x
 
     GRAD_KERNELS = {0: "k_ppo_grad_ws", 1: "k_ppo_grad_tp", 2: "k_ppo_grad_tp1",
-                    3: "k_ppo_grad_mfma"}
+                    3: "k_ppo_grad_mfma", 4: "k_net_grad"}
 
     def grad_kernel(self, minibatch=0):
         """wk_grad_kernel: the name of the gradient kernel the update launches at this per-GPU
