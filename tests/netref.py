@@ -8,6 +8,8 @@ infrastructure only (numpy), the counterpart of tests/ref64.py for NetworkKernel
   * adam32: DenseLayer.Adam (DenseLayer.cs:125-159) in fp32, the bias corrections in double.
   * train_batch_grad64: PPOAgent.Train(Batch) (PPOAgent.cs:218-346) in float64, returning
     (grad, abs_sum, critic_diag, actor_diag, skipped) like ref64.train_batch_grad64.
+  * train_batch_grad32: the same code with every array and constant in fp32 -- what a correct
+    fp32 evaluation may differ from float64 by; tests/net_cases.py chooses inputs on it.
 
 Parameter layout: the .weights order -- critic dense layers, then the actor's, each W (out x in,
 row-major) then b.
@@ -30,6 +32,25 @@ NETS = {
     "max": ("Input |128| (LeakyReLU) |128| (ReLU) |128| (TanH) |1| Output",
             "Input |128| (ReLU) |128| (TanH) |128| (LeakyReLU) |4| (TanH) Output"),
 }
+# the edge networks of tests/test_gpu_net_edges.py: widths next to the kernels' tile edges (out
+# against 16; in against 4, 16 and 32), widths 1 to 3, stacked activations, and the pairs in which
+# one network alone decides the rows of the activation cache
+NETS.update({
+    "edge16": ("Input |16| (ReLU) |15| (TanH) |1| Output",
+               "Input |15| (LeakyReLU) |16| (ReLU) |17| (TanH) |4| Output"),
+    "edge32": ("Input |32| (TanH) |31| (LeakyReLU) |1| Output",
+               "Input |31| (TanH) |32| (LeakyReLU) |33| (ReLU) |4| Output"),
+    "edge64": ("Input |65| (TanH) |63| (LeakyReLU) |1| Output",
+               "Input |63| (LeakyReLU) |64| (TanH) |65| (LeakyReLU) |4| (TanH) Output"),
+    "edge128": ("Input |127| (LeakyReLU) |128| (TanH) |1| Output",
+                "Input |128| (TanH) |127| (LeakyReLU) |4| Output"),
+    "narrow": ("Input |1| (TanH) |1| Output", "Input |1| |2| (TanH) |3| |4| Output"),
+    "stacked": ("Input (TanH) (LeakyReLU) |9| (TanH) (TanH) (LeakyReLU) |1| Output",
+                "Input (ReLU) |4| Output"),
+    "big_critic": (NETS["max"][0], NETS["tiny"][1]),
+    "big_actor": (NETS["tiny"][0], NETS["max"][1]),
+})
+EDGE_NAMES = ["edge16", "edge32", "edge64", "edge128", "narrow", "stacked", "big_critic", "big_actor"]
 
 
 def layers(dsl):
@@ -122,22 +143,23 @@ def _backward64(L, P, cache, g):
     return flat(G), flat(A)
 
 
-def train_batch_grad64(critic, actor, w, S, A, L, G, Ad, b_div, log_std=-1.0, eps_clip=0.3):
-    """Returns (grad, abs_sum, critic_diag, actor_diag, skipped) in float64; abs_sum[p] is the
-    sum over samples of |contribution to grad[p]|."""
-    w = np.asarray(w, np.float64)
-    S, A, L = (np.asarray(x, np.float64) for x in (S, A, L))
-    G, Ad = np.asarray(G, np.float64), np.asarray(Ad, np.float64)
+def _train_batch_grad(T, critic, actor, w, S, A, L, G, Ad, b_div, log_std=-1.0, eps_clip=0.3):
+    """PPOAgent.Train(Batch) with every array and constant of type T (np.float64 / np.float32)"""
+    w = np.asarray(w, T)
+    S, A, L = (np.asarray(x, T) for x in (S, A, L))
+    G, Ad = np.asarray(G, T), np.asarray(Ad, T)
+    b_div, one, two = T(b_div), T(1), T(2)
     nc = n_params(critic)
     Lc, La = layers(critic), layers(actor)
     Pc, Pa = split(critic, w[:nc]), split(actor, w[nc:])
-    std = float(np.float32(np.exp(np.float32(log_std))))  # MathF.Exp(-1) in fp32
-    lp_const = float(-np.log(np.float32(std)) - np.log(np.sqrt(2 * np.pi)))
+    std = T(np.float32(np.exp(np.float32(log_std))))  # MathF.Exp(-1) in fp32
+    lp_const = T(-np.log(np.float32(std)) - np.log(np.sqrt(2 * np.pi)))
     V, cc = _forward64(Lc, Pc, S)
     mean, ca = _forward64(La, Pa, S)
-    up, lo = 1.0 + eps_clip, 1.0 - eps_clip
-    lp = lp_const - ((A - mean) / std) ** 2 / 2.0
-    r = np.exp(lp - L)
+    up, lo = one + T(eps_clip), one - T(eps_clip)
+    lp = lp_const - ((A - mean) / std) ** 2 / two
+    with np.errstate(over="ignore"):  # (fp32: a skipped sample's ratio is exp(197) = inf)
+        r = np.exp(lp - L)
     cr = np.clip(r, lo, up)
     Acol = Ad[:, None]
     partA = (r * Acol <= cr * Acol) * Acol
@@ -146,14 +168,36 @@ def train_batch_grad64(critic, actor, w, S, A, L, G, Ad, b_div, log_std=-1.0, ep
     l = -(partA + partB * partC)
     eo = np.exp(L)
     use = ~(np.float32(0) == np.exp(np.asarray(L, np.float32))).any(axis=1)  # fp32 underflow
-    act = np.exp(lp) * ((A - mean) / std ** 2) * (l / np.where(eo == 0, 1.0, eo)) / b_div
-    crit = 2.0 * (V - G[:, None]) / b_div
-    act[~use] = 0.0
-    crit[~use] = 0.0
+    act = np.exp(lp) * ((A - mean) / std ** 2) * (l / np.where(eo == 0, one, eo)) / b_div
+    crit = two * (V - G[:, None]) / b_div
+    act[~use] = 0
+    crit[~use] = 0
     gc, ac = _backward64(Lc, Pc, cc, crit)
     ga, aa = _backward64(La, Pa, ca, act)
+    assert T is np.float64 or all(x.dtype == T for x in (gc, ac, ga, aa, act, crit)), "not all fp32"
     return (np.concatenate([gc, ga]), np.concatenate([ac, aa]), crit.sum(), act.mean(axis=1).sum(),
             int((~use).sum()))
+
+
+def policy64(actor, w_actor, S, A, log_std=-1.0):
+    """float64 (mean, per-dimension log-density of the actions A) of the actor at the states S"""
+    La = layers(actor)
+    mean, _ = _forward64(La, split(actor, np.asarray(w_actor, np.float64)), np.asarray(S, np.float64))
+    std = float(np.float32(np.exp(np.float32(log_std))))
+    lp_const = float(-np.log(np.float32(std)) - np.log(np.sqrt(2 * np.pi)))
+    return mean, lp_const - ((np.asarray(A, np.float64) - mean) / std) ** 2 / 2.0
+
+
+def train_batch_grad64(critic, actor, w, S, A, L, G, Ad, b_div, log_std=-1.0, eps_clip=0.3):
+    """Returns (grad, abs_sum, critic_diag, actor_diag, skipped) in float64; abs_sum[p] is the
+    sum over samples of |contribution to grad[p]|."""
+    return _train_batch_grad(np.float64, critic, actor, w, S, A, L, G, Ad, b_div, log_std, eps_clip)
+
+
+def train_batch_grad32(critic, actor, w, S, A, L, G, Ad, b_div, log_std=-1.0, eps_clip=0.3):
+    """the same math with every array and constant in np.float32: what a correct fp32 evaluation
+    may differ from float64 by (tests/net_cases.py chooses inputs on it)"""
+    return _train_batch_grad(np.float32, critic, actor, w, S, A, L, G, Ad, b_div, log_std, eps_clip)
 
 
 def adam32(w, m, v, g, t, alpha=1e-3, beta1=0.9, beta2=0.999, eps=1e-8):

@@ -15,6 +15,9 @@ prints its worst ratio (pytest -s; measured: at most 0.213, DESIGN.md "General n
 cases' inputs are the ones those constants were worked out on (_case).  The bound prices fp32
 summation, not a ReLU / LeakyReLU pre-activation within fp32 rounding of zero, where fp32 and
 float64 take different branches of the derivative: such a sample is a property of the inputs drawn.
+
+Widths at the tile edges, the block / reduction-group edges, more skip patterns, the surrogate's six
+cells, Adam's moments and rollouts across episode ends: tests/test_gpu_net_edges.py.
 """
 import numpy as np
 import pytest
