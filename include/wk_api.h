@@ -86,7 +86,8 @@ typedef struct wk_config {
   int UseGAE;               /* 0 */
   int NormalizeAdvantages;  /* 0 */
   float Gamma;              /* 0.9 */
-  float Lambda;             /* 0.95 */
+  float Lambda;             /* 0.95; takes effect with ReturnsMode = 1 only: the reference never
+                               chains its GAE (PPOAgent.cs:414-434), and ReturnsMode 0 restates it */
   float Epsilon;            /* 0.3 */
   float LogStandardDeviation; /* -1 */
   float Alpha;              /* 1e-3 */
@@ -118,6 +119,15 @@ typedef struct wk_config {
                                (wk_comm_init, wk_comm_init_host, wk_comm_ipc_handle,
                                wk_comm_init_ipc) returns WK_ERR_CONFIG on such a context.  Not
                                part of the JSON document */
+  int ReturnsMode;          /* 0: the reference's returns / advantages (PPOAgent.cs:414-498): the GAE
+                               chain is never carried (every advantage is the one-step TD error,
+                               Lambda unused) and every reverse scan starts from 0, at a horizon
+                               cut as at an episode end.  1: the standard estimators -- chained
+                               GAE(Lambda), and the scan starts from the critic's value of each
+                               walker's observation after the last recorded step (the bootstrap
+                               values, wk_get / wk_set_bootstrap_values); a terminal step still
+                               resets the scan to 0, an episode ended by MaxTimesteps included.
+                               Anything else is WK_ERR_CONFIG.  Not part of the JSON document */
 } wk_config;
 
 /* The host-only fields of the reference's JSON configuration (SerializableHyperparameters,
@@ -388,6 +398,19 @@ int wk_set_trajectory(wk_ctx* ctx, int horizon, const float* states, const float
                       const float* logp, const float* rewards, const uint8_t* dones,
                       const float* values);
 int wk_compute_returns(wk_ctx* ctx);
+/* The bootstrap values of a ReturnsMode = 1 context: v[e] is the value the reverse scan of
+ * walker e starts from, the critic's estimate of the state after the trajectory's last row (not
+ * used when that row is terminal).  They belong to the trajectory buffer: wk_rollout fills them
+ * with wk_value of every walker's observation after its last env-step (post-reset after a
+ * terminal step), wk_set_trajectory and wk_checkpoint_load invalidate them, wk_snapshot leaves
+ * them alone.  wk_set_bootstrap_values (after wk_rollout or wk_set_trajectory) replaces them and
+ * marks the returns stale: the next wk_compute_returns / wk_ppo_update recomputes them.  After
+ * wk_set_trajectory, wk_compute_returns, wk_ppo_update and wk_time_gradient* return WK_ERR_STATE
+ * until the values are set: a host that feeds complete episodes passes zeros, one that cuts
+ * episodes passes wk_value of the next observations.  Both calls are WK_ERR_STATE on a
+ * ReturnsMode = 0 context, wk_get_bootstrap_values also while no valid values exist. */
+int wk_get_bootstrap_values(wk_ctx* ctx, float* v /* n_env */);
+int wk_set_bootstrap_values(wk_ctx* ctx, const float* v /* n_env */);
 int wk_ppo_update(wk_ctx* ctx, const wk_ppo_args* args, float* critic_diag, float* actor_diag);
 /* Train(Batch) on caller data: B samples, divisor b_div; grads_out (optional, WK_NPARAM)
  * receives the accumulated gradient before Adam. Returns skipped-sample count in *skipped. */

@@ -38,7 +38,9 @@ public struct WkConfig
     public int Horizon, Minibatch, MinibatchGlobal, EnvOffset, RandomizeStart, RandomizeMaterial;
     // LanesPerWalker: 0 = auto (4-lane split leg pairs up to 16,384 walkers, else the 2-lane leg split), 1 / 2 / 4 / 16 lanes.
     // NetworkKernels: 0 = the built-in kernels (default network strings only), 1 = the general kernels (any valid string within the limits)
-    public int LanesPerWalker, NetworkKernels;
+    // ReturnsMode: 0 = the reference's returns (GAE never chained, 0 at every horizon cut), 1 = chained GAE(Lambda) and the
+    // critic's value at the cut (wk_get / wk_set_bootstrap_values) -- a host that trains on complete episodes passes zeros
+    public int LanesPerWalker, NetworkKernels, ReturnsMode;
 }
 
 // SerializableHyperparameters' host-only fields (Hyperparameters.cs:11-77)
@@ -202,6 +204,8 @@ public static class Wk
     [DllImport(Lib)] public static extern int wk_get_trajectory(IntPtr ctx, float[]? states, float[]? actions, float[]? logp, float[]? rewards, byte[]? dones, float[]? values, float[]? returns, float[]? advantages);
     [DllImport(Lib)] public static extern int wk_set_trajectory(IntPtr ctx, int horizon, float[] states, float[] actions, float[] logp, float[] rewards, byte[] dones, float[] values);
     [DllImport(Lib)] public static extern int wk_compute_returns(IntPtr ctx);
+    [DllImport(Lib)] public static extern int wk_get_bootstrap_values(IntPtr ctx, float[] v);
+    [DllImport(Lib)] public static extern int wk_set_bootstrap_values(IntPtr ctx, float[] v);
     [DllImport(Lib)] public static extern int wk_ppo_update(IntPtr ctx, ref WkPpoArgs args, out float criticDiag, out float actorDiag);
     [DllImport(Lib)] public static extern int wk_train_batch(IntPtr ctx, int B, float bDiv, float[] states, float[] actions, float[] logpOld, float[] returns, float[] adv, out float criticDiag, out float actorDiag, float[]? gradsOut, int applyAdam, out int skipped);
     [DllImport(Lib)] public static extern int wk_minibatch_gradient(IntPtr ctx, int B, float bDiv, float[] states, float[] actions, float[] logpOld, float[] returns, float[] adv, out float criticDiag, out float actorDiag, float[]? gradsOut, out int skipped);

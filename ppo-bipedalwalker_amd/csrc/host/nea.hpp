@@ -114,7 +114,10 @@ namespace Walker {
 namespace PPO {
 // Hyperparameters (Hyperparameters.cs:80-121): static-like defaults as a value type.
 // c.NetworkKernels = 1 with c.CriticNeuralNetwork / c.ActorNeuralNetwork set runs any valid
-// network string on the general kernels (the reference's network menu, ConsoleRenderer.cs:188-189)
+// network string on the general kernels (the reference's network menu, ConsoleRenderer.cs:188-189).
+// c.ReturnsMode = 1 selects chained GAE(Lambda) and the critic's value at a horizon cut
+// (wk_get / wk_set_bootstrap_values); 0, the default, is the reference's arithmetic, and this
+// host, which trains on what wk_rollout recorded, needs no further call in either mode
 struct Hyperparameters {
   wk_config c;
   Hyperparameters() { wk_config_defaults(&c); }

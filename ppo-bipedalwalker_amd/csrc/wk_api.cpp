@@ -66,6 +66,9 @@ struct wk_ctx {
   float *ts = nullptr, *ta = nullptr, *tlp = nullptr, *tr = nullptr, *tv = nullptr, *tret = nullptr, *tadv = nullptr;
   uint8_t* td = nullptr;
   bool returns_valid = false;
+  // ReturnsMode = 1: the value each walker's reverse scan starts from (part of the trajectory)
+  float* vlast = nullptr;     // [n]
+  bool vlast_valid = false;
   // data collection (ConsoleRenderer.AddTotalEpisodeReward / AddCriticLoss / AddActorLoss)
   int collect = 1;
   uint32_t rollout_steps = 0;  // env-steps taken by wk_rollout so far (episode log clock)
@@ -244,6 +247,7 @@ void wk_config_defaults(wk_config* c) {
   c->RandomizeStart = 0;
   c->RandomizeMaterial = 0;
   c->NetworkKernels = 0;
+  c->ReturnsMode = 0;
 }
 
 const char* wk_version(void) { return "wk 0.1 (gfx950)"; }
@@ -287,6 +291,8 @@ static int validate(const wk_config* c, std::string& why) {
     wk::NetSpec ns;
     if (!wk::net_spec(c->CriticNeuralNetwork, c->ActorNeuralNetwork, ns, why)) return WK_ERR_CONFIG;
   }
+  if (c->ReturnsMode != 0 && c->ReturnsMode != 1)
+    return bad("ReturnsMode must be 0 (the reference's returns) or 1 (chained GAE, bootstrap at the cut)");
   if (c->Horizon <= 0) return bad("Horizon must be > 0");
   if (c->Minibatch < 0) return bad("Minibatch must be >= 0");
   if (c->LanesPerWalker != 0 && c->LanesPerWalker != 1 && c->LanesPerWalker != 2 &&
@@ -440,6 +446,7 @@ int wk_create(const wk_config* cfg, int device, int n_env, uint64_t seed, wk_ctx
   ALLOC(x->tret, sizeof(float) * n * T);
   ALLOC(x->tadv, sizeof(float) * n * T);
   ALLOC(x->td, n * T);
+  if (c.ReturnsMode == 1) ALLOC(x->vlast, sizeof(float) * n);
   x->ep_cap = (uint64_t)n * T;  // one rollout's worst case: every env-step ends an episode
   x->loss_cap = 1u << 16;
   ALLOC(x->ep_acc, sizeof(double) * n);
@@ -529,7 +536,8 @@ int wk_destroy(wk_ctx* c) {
   void* bufs[] = {c->st, c->dxoff, c->mat, c->rng_t, c->W, c->Wz, c->m, c->v, c->grad, c->ts, c->ta,
                   c->tlp, c->tr, c->tv, c->tret, c->tadv, c->td, c->partial, c->scratch, c->scratch2,
                   c->ep_acc, c->ep_len, c->ep_scratch, c->ep_rowcnt, c->ep_count, c->ep_log,
-                  c->loss_log, c->props, c->snap, c->counts, c->order, c->order_cnt, c->pace, c->net_dev};
+                  c->loss_log, c->props, c->snap, c->counts, c->order, c->order_cnt, c->pace, c->net_dev,
+                  c->vlast};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1201,11 +1209,37 @@ int wk_value(wk_ctx* c, int n, const float* obs, float* v) {
   return policy_impl(c, n, obs, nullptr, nullptr, nullptr, nullptr, nullptr, v);
 }
 
+// ReturnsMode = 1: the critic's value of every walker's current observation (post-reset after a
+// terminal step) into vlast, with the kernels of wk_value -- bit-equal to wk_value(wk_get_obs())
+static int bootstrap_values(wk_ctx* c) {
+  if (ensure(c, &c->scratch, &c->scratch_bytes, sizeof(float) * 12 * c->n)) return WK_ERR_HIP;
+  float* obs = (float*)c->scratch;
+  ProfScope ps(c, PK_RET);
+  HIPCHK(c, wk::launch_get_obs(c->P, c->st, obs, c->stream));
+  if (c->general)
+    HIPCHK(c, wk::launch_net_policy(c->P, c->net_dev, c->act_rows, c->W, c->lp_const, c->n, obs, nullptr,
+                                    nullptr, nullptr, nullptr, nullptr, c->vlast, c->stream));
+  else
+    HIPCHK(c, wk::launch_policy(c->P, c->W, c->lp_const, c->n, obs, nullptr, nullptr, nullptr, nullptr,
+                                nullptr, c->vlast, c->stream));
+  c->vlast_valid = true;
+  return WK_OK;
+}
+
 static int returns_impl(wk_ctx* c) {
+  if (c->cfg.ReturnsMode == 1 && !c->vlast_valid) {
+    SETERR(c, "ReturnsMode 1: the trajectory has no bootstrap values -- call wk_set_bootstrap_values "
+              "(zeros for complete episodes, wk_value of the next observations at a cut)");
+    return WK_ERR_STATE;
+  }
   {
     ProfScope ps(c, PK_RET);
-    HIPCHK(c, wk::launch_returns(c->n, c->T_valid, c->cfg.UseGAE, c->cfg.Gamma, c->cfg.Lambda,
-                                 c->tr, c->tv, c->td, c->tret, c->tadv, c->stream));
+    if (c->cfg.ReturnsMode == 1)
+      HIPCHK(c, wk::launch_returns_std(c->n, c->T_valid, c->cfg.UseGAE, c->cfg.Gamma, c->cfg.Lambda,
+                                       c->tr, c->tv, c->td, c->vlast, c->tret, c->tadv, c->stream));
+    else
+      HIPCHK(c, wk::launch_returns(c->n, c->T_valid, c->cfg.UseGAE, c->cfg.Gamma, c->cfg.Lambda,
+                                   c->tr, c->tv, c->td, c->tret, c->tadv, c->stream));
   }
   if (c->cfg.NormalizeAdvantages)
     HIPCHK(c, wk::launch_normalize(c->tadv, c->n * c->T_valid, c->cfg.Epsilon, c->stream));
@@ -1241,6 +1275,8 @@ int wk_rollout(wk_ctx* c, int horizon) {
     HIPCHK(c, wk::launch_episode_log(e, c->stream));
   }
   c->rollout_steps += (uint32_t)horizon;
+  if (c->cfg.ReturnsMode == 1)
+    if (int r = bootstrap_values(c)) return r;
   return returns_impl(c);
 }
 
@@ -1298,6 +1334,35 @@ int wk_set_trajectory(wk_ctx* c, int horizon, const float* s, const float* a, co
   HIPCHK(c, hipMemcpy(c->td, d, cnt, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(c->tv, v, sizeof(float) * cnt, hipMemcpyHostToDevice));
   c->T_valid = horizon;
+  c->returns_valid = false;
+  c->vlast_valid = false;
+  return WK_OK;
+}
+
+int wk_get_bootstrap_values(wk_ctx* c, float* v) {
+  DevGuard dg_(c);
+  if (!c || !v) return WK_ERR_ARG;
+  if (c->cfg.ReturnsMode != 1) { SETERR(c, "wk_get_bootstrap_values needs ReturnsMode = 1"); return WK_ERR_STATE; }
+  if (!c->vlast_valid) {
+    SETERR(c, "no bootstrap values: call wk_rollout or wk_set_bootstrap_values first");
+    return WK_ERR_STATE;
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(v, c->vlast, sizeof(float) * c->n, hipMemcpyDeviceToHost));
+  return WK_OK;
+}
+
+int wk_set_bootstrap_values(wk_ctx* c, const float* v) {
+  DevGuard dg_(c);
+  if (!c || !v) return WK_ERR_ARG;
+  if (c->cfg.ReturnsMode != 1) { SETERR(c, "wk_set_bootstrap_values needs ReturnsMode = 1"); return WK_ERR_STATE; }
+  if (c->T_valid <= 0) {
+    SETERR(c, "wk_set_bootstrap_values before wk_rollout / wk_set_trajectory");
+    return WK_ERR_STATE;
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(c->vlast, v, sizeof(float) * c->n, hipMemcpyHostToDevice));
+  c->vlast_valid = true;
   c->returns_valid = false;
   return WK_OK;
 }
@@ -2394,6 +2459,7 @@ int wk_checkpoint_load(wk_ctx* c, const char* path) {
   c->rollout_steps = h.rollout_steps;
   c->T_valid = 0;
   c->returns_valid = 0;
+  c->vlast_valid = false;
   HIPCHK(c, upload_image(c));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return WK_OK;

@@ -188,6 +188,10 @@ int xch_blocks();
 size_t xch_region_bytes();
 hipError_t launch_reduce_xch_adam(const XchArgs& x, hipStream_t s);
 hipError_t launch_normalize(float* x, int n, float eps, hipStream_t s);
+// ReturnsMode = 1 (k_returns_std): chained GAE(lambda), the scan bootstrapped from vlast[n]
+hipError_t launch_returns_std(int n, int T, int use_gae, float gamma, float lambda, const float* r,
+                              const float* v, const uint8_t* d, const float* vlast, float* ret,
+                              float* adv, hipStream_t s);
 hipError_t launch_xavier(float* W, uint64_t seed, hipStream_t s);
 
 // the general networks' kernels (wk_net.hip; NetworkKernels = 1).  nets: device copy of

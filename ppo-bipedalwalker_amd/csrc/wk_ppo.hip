@@ -326,6 +326,43 @@ __global__ __launch_bounds__(RG * QB) void k_grad_reduce_fused(const float* __re
   reduce_job<ADAM>(blockIdx.x, threadIdx.x, partial, nblocks, grad, a, gs);
 }
 
+// ReturnsMode = 1: the standard estimators, with k_returns' mapping (one lane per walker, reverse
+// scan over the [T][n] rows).  The scan starts from vlast[e], the critic's value of the state
+// after the last row, instead of 0, and the GAE chain is carried (k_returns restates the
+// reference, whose nextGae stays 0).  A done step assigns 0 -- no multiply, so a non-finite
+// bootstrap value or later row never passes an episode end.  The operations are written out one
+// by one (the build does not contract them): tests/retref.py restates them in float32 bit for bit.
+__global__ void k_returns_std(int n, int T, int use_gae, float gamma, float lambda,
+                              const float* __restrict__ r, const float* __restrict__ v,
+                              const uint8_t* __restrict__ done, const float* __restrict__ vlast,
+                              float* __restrict__ ret, float* __restrict__ adv) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  if (!use_gae) {
+    float disc = vlast[e];
+    for (int t = T - 1; t >= 0; t--) {
+      const size_t i = (size_t)t * n + e;
+      if (done[i]) disc = 0.0f;
+      disc = r[i] + (disc * gamma);
+      ret[i] = disc;
+      adv[i] = disc - v[i];
+    }
+  } else {
+    float nextValue = vlast[e], nextGae = 0.0f;
+    for (int t = T - 1; t >= 0; t--) {
+      const size_t i = (size_t)t * n + e;
+      if (done[i]) { nextValue = 0.0f; nextGae = 0.0f; }
+      const float cur = v[i];
+      const float delta = r[i] + (gamma * nextValue) - cur;
+      const float gae = delta + (gamma * lambda * nextGae);
+      adv[i] = gae;
+      ret[i] = gae + cur;
+      nextValue = cur;
+      nextGae = gae;
+    }
+  }
+}
+
 // Normalize (PPOAgent.cs:461-472): LINQ Average/Sum accumulate in double
 __global__ void k_normalize(float* x, int n, float eps_clip) {
   __shared__ double red[1024];
@@ -588,6 +625,13 @@ hipError_t launch_adam(const AdamArgs& a, hipStream_t s) {
 }
 hipError_t launch_normalize(float* x, int n, float eps, hipStream_t s) {
   hipLaunchKernelGGL(k_normalize, dim3(1), dim3(1024), 0, s, x, n, eps);
+  return hipGetLastError();
+}
+hipError_t launch_returns_std(int n, int T, int use_gae, float gamma, float lambda, const float* r,
+                              const float* v, const uint8_t* d, const float* vlast, float* ret,
+                              float* adv, hipStream_t s) {
+  hipLaunchKernelGGL(k_returns_std, dim3((n + 255) / 256), dim3(256), 0, s, n, T, use_gae, gamma,
+                     lambda, r, v, d, vlast, ret, adv);
   return hipGetLastError();
 }
 hipError_t launch_xavier(float* W, uint64_t seed, hipStream_t s) {

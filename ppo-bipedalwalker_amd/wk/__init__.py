@@ -46,6 +46,7 @@ EXPORTS = [
     "wk_comm_xch_profile", "wk_comm_xch_stamps", "wk_check_state", "wk_take_actions",
     "wk_object_update", "wk_joint_step", "wk_body_order",
     "wk_net_param_count", "wk_num_params", "wk_format_weights_net", "wk_parse_weights_net",
+    "wk_get_bootstrap_values", "wk_set_bootstrap_values",
 ]
 
 
@@ -72,6 +73,7 @@ class WkConfig(C.Structure):
         ("Minibatch", C.c_int), ("MinibatchGlobal", C.c_int), ("EnvOffset", C.c_int),
         ("RandomizeStart", C.c_int), ("RandomizeMaterial", C.c_int),
         ("LanesPerWalker", C.c_int), ("NetworkKernels", C.c_int),
+        ("ReturnsMode", C.c_int),
     ]
 
 
@@ -274,6 +276,8 @@ def load_library(path=None):
         "wk_format_weights_net": (I, [C.c_char_p, C.c_char_p, P, C.c_char_p, C.c_size_t, C.c_char_p,
                                       C.c_size_t]),
         "wk_parse_weights_net": (I, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, P]),
+        "wk_get_bootstrap_values": (I, [P, P]),
+        "wk_set_bootstrap_values": (I, [P, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -658,6 +662,19 @@ class Engine:
 
     def compute_returns(self):
         self._chk(self.lib.wk_compute_returns(self.h), "wk_compute_returns")
+
+    def get_bootstrap_values(self):
+        """wk_get_bootstrap_values (ReturnsMode = 1): the value each walker's reverse scan starts
+        from -- after a rollout, value(get_obs())"""
+        v = np.empty(self.n, np.float32)
+        self._chk(self.lib.wk_get_bootstrap_values(self.h, _ptr(v)), "wk_get_bootstrap_values")
+        return v
+
+    def set_bootstrap_values(self, v):
+        """wk_set_bootstrap_values (ReturnsMode = 1): replace them (zeros for complete episodes);
+        the next compute_returns / ppo_update recomputes the returns"""
+        v = _f32(v, (self.n,))
+        self._chk(self.lib.wk_set_bootstrap_values(self.h, _ptr(v)), "wk_set_bootstrap_values")
 
     def ppo_update(self, epochs=0, minibatch=0, minibatch_global=0, update_index=0, sync=True):
         """Whole PPO update; returns the last minibatch's (critic, actor) diagnostics, or

@@ -1,0 +1,92 @@
+"""CPU: the returns / advantages restatement (tests/retref.py) and the ReturnsMode field's host side.
+
+The properties that make ReturnsMode = 1 the standard estimator, checked on the restatement the
+GPU tests (tests/test_gpu_returns.py) compare the kernel with bit for bit: with zero bootstrap
+values the Monte-Carlo scan is the reference's; GAE(1) is the bootstrapped Monte-Carlo return;
+nothing passes an episode end; Lambda is live in mode 1 and dead in mode 0.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import retref
+
+F = np.float32
+GAMMA, LAMBDA = 0.9, 0.95
+
+
+def _case(seed, T=64, n=33, rate=0.1):
+    g = np.random.default_rng(seed)
+    r = g.uniform(-40, 80, (T, n)).astype(F)
+    v = (10 * g.standard_normal((T, n))).astype(F)
+    d = (g.random((T, n)) < rate).astype(np.uint8)
+    vlast = (10 * g.standard_normal(n)).astype(F)
+    return r, v, d, vlast
+
+
+def test_mc_with_zero_bootstrap_is_the_reference_scan():
+    r, v, d, _ = _case(1)
+    a = retref.returns32(1, 0, GAMMA, LAMBDA, r, v, d, np.zeros(r.shape[1], F))
+    b = retref.returns32(0, 0, GAMMA, LAMBDA, r, v, d)
+    for x, y in zip(a, b):
+        assert x.dtype == F and x.tobytes() == y.tobytes()
+
+
+def test_gae_lambda_one_is_the_bootstrapped_mc_return():
+    r, v, d, vlast = _case(2)
+    ret_gae, _ = retref.returns64(1, 1, GAMMA, 1.0, r, v, d, vlast)
+    ret_mc, _ = retref.returns64(1, 0, GAMMA, 1.0, r, v, d, vlast)
+    np.testing.assert_allclose(ret_gae, ret_mc, rtol=1e-12, atol=0)
+
+
+@pytest.mark.parametrize("use_gae", [0, 1])
+@pytest.mark.parametrize("ft", ["returns32", "returns64"])
+def test_nothing_passes_a_done_step(use_gae, ft):
+    """changing r, v or vlast after a done step changes nothing at or before it"""
+    fn = getattr(retref, ft)
+    r, v, d, vlast = _case(3, T=24, n=9, rate=0.0)
+    cut = 11
+    d[cut] = 1  # every walker's episode ends at row `cut`
+    base = fn(1, use_gae, GAMMA, LAMBDA, r, v, d, vlast)
+    r2, v2, vlast2 = r.copy(), v.copy(), vlast.copy()
+    r2[cut + 1:] += F(7)
+    v2[cut + 1:] = np.nan
+    vlast2[:] = np.inf
+    moved = fn(1, use_gae, GAMMA, LAMBDA, r2, v2, d, vlast2)
+    for x, y in zip(base, moved):
+        assert np.isfinite(x[:cut + 1]).all()
+        assert x[:cut + 1].tobytes() == y[:cut + 1].tobytes()
+        assert not np.array_equal(x[cut + 1:], y[cut + 1:], equal_nan=True)
+
+
+def test_lambda_is_live_in_mode_1_only():
+    r, v, d, vlast = _case(4)
+    adv = {(m, lam): retref.returns32(m, 1, GAMMA, lam, r, v, d, vlast)[1]
+           for m in (0, 1) for lam in (0.5, 0.95)}
+    assert adv[0, 0.5].tobytes() == adv[0, 0.95].tobytes()  # the reference never carries the chain
+    assert not np.array_equal(adv[1, 0.5], adv[1, 0.95])
+    # mode 0's advantages are the one-step TD errors, i.e. mode 1 cut off with Lambda -> 0 apart
+    # from the bootstrap of the last row
+    T = r.shape[0]
+    last_done = d[T - 1].astype(bool)
+    np.testing.assert_array_equal(adv[0, 0.5][T - 1][last_done], adv[1, 0.5][T - 1][last_done])
+
+
+def test_returns_mode_2_is_refused_without_a_device(wk):
+    lib = wk.load_library()
+    cfg = wk.default_config(ReturnsMode=2)
+    h = C.c_void_p()
+    rc = lib.wk_create(C.byref(cfg), 0, 8, 1, C.byref(h))
+    assert rc == -3  # WK_ERR_CONFIG
+    assert "ReturnsMode" in lib.wk_last_error(None).decode()
+    assert not h.value
+
+
+def test_returns_mode_defaults_to_0_and_stays_out_of_the_json_document(wk):
+    assert wk.default_config().ReturnsMode == 0
+    assert "ReturnsMode" not in wk.config_to_json()
+    cfg = wk.default_config(ReturnsMode=1)
+    cfg, _, fixes = wk.config_from_json(wk.config_to_json(), cfg=cfg)
+    assert cfg.ReturnsMode == 1 and not fixes  # the document keeps the field's value
+    assert wk.WkConfig.ReturnsMode.offset == wk.WkConfig.NetworkKernels.offset + 4
