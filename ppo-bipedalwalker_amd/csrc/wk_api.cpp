@@ -10,6 +10,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -81,14 +82,19 @@ struct wk_ctx {
   uint64_t ep_cap = 0;
   float* loss_log = nullptr;      // [loss_cap][2] (critic, actor) per PPO update
   uint64_t loss_count = 0, loss_cap = 0;
-  // scratch
-  float* partial = nullptr; size_t partial_floats = 0;
-  void* scratch = nullptr; size_t scratch_bytes = 0;
-  void* scratch2 = nullptr; size_t scratch2_bytes = 0;
+  // dev_alloc's record: the addresses of the pointers whose buffers wk_destroy frees (the IPC
+  // region xch and its peers have their own calls); props takes its block over from props_next
+  std::vector<void**> owned{(void**)&props};
+  // scratch.  Two buffers for temporaries, because net_sampled (scratch) runs inside callers that
+  // hold pointers into their own carve-up (wk_step_sampled: scratch2), and growing one frees it
+  float* partial = nullptr; size_t partial_bytes = 0;
+  void* scratch = nullptr; size_t scratch_bytes = 0;  // net_sampled, wk_get_obs, wk_reset, bootstrap_values, wk_allreduce_test
+  void* scratch2 = nullptr; size_t scratch2_bytes = 0;  // the entry points that carve
   // scene props (wk_set_scene): descriptions, kernel constants, [n][pstride] state
   std::vector<wk_prop> scene_desc;
   wk::SceneDev scene{};
   float* props = nullptr;
+  float* props_next = nullptr;  // wk_set_scene's new block until it replaces props
   // wk_snapshot: one device block holding every snapshotted buffer, plus the host counters
   void* snap = nullptr; size_t snap_bytes = 0;
   int snap_adam_t = 0; uint32_t snap_rollout_steps = 0; uint64_t snap_loss_count = 0;
@@ -206,15 +212,46 @@ static void prof_drain(wk_ctx* c) {
   c->pending.clear();
 }
 
-static int ensure(wk_ctx* c, void** p, size_t* have, size_t need) {
+// The one allocator: hipMalloc through `p`, recording p's address (once).  wk_destroy frees what
+// the recorded pointers hold by then, so a buffer replaced through its pointer is freed once.
+template <class T>
+static hipError_t dev_alloc(wk_ctx* c, T** p, size_t bytes) {
+  const hipError_t e = hipMalloc((void**)p, bytes);
+  if (e == hipSuccess && std::find(c->owned.begin(), c->owned.end(), (void**)p) == c->owned.end())
+    c->owned.push_back((void**)p);
+  return e;
+}
+
+// a lazily sized buffer: at least `need` bytes behind *p (the contents are not kept)
+template <class T>
+static int ensure(wk_ctx* c, T** p, size_t* have, size_t need) {
   if (*have >= need) return 0;
   if (*p) (void)hipFree(*p);
   *p = nullptr;
   *have = 0;
-  HIPCHK(c, hipMalloc(p, need));
+  HIPCHK(c, dev_alloc(c, p, need));
   *have = need;
   return 0;
 }
+
+// The bump carver over a scratch buffer: the caller lists its pieces once (where the pointer goes,
+// how many bytes); each is aligned to 256 bytes, and a piece of no bytes gets null.
+struct Piece { void* out; size_t bytes; };  // out: the address of the pointer
+static int carve(wk_ctx* c, void** buf, size_t* have, std::initializer_list<Piece> pieces) {
+  const auto span = [](const Piece& p) { return (p.bytes + 255) & ~(size_t)255; };
+  size_t total = 0;
+  for (const Piece& p : pieces) total += span(p);
+  if (ensure(c, buf, have, total)) return WK_ERR_HIP;
+  char* at = (char*)*buf;
+  for (const Piece& p : pieces) {
+    *(void**)p.out = p.bytes ? at : nullptr;
+    at += span(p);
+  }
+  return WK_OK;
+}
+
+// a device buffer and its size: the rows of wk_snapshot's block and of the checkpoint file
+struct Seg { void* p; size_t bytes; };
 
 extern "C" {
 
@@ -325,6 +362,15 @@ static hipError_t upload_image(wk_ctx* c) {
   return c->general ? hipSuccess : wk::launch_swizzle(c->W, c->Wz, c->stream);
 }
 
+// the eight [T][n] trajectory rows in wk_get_trajectory's argument order, with bytes per sample
+struct TrajRow { const char* name; void** p; size_t bytes; };
+static std::array<TrajRow, 8> traj_rows(wk_ctx* c) {
+  const size_t f = sizeof(float);
+  return {{{"ts", (void**)&c->ts, 12 * f}, {"ta", (void**)&c->ta, 4 * f}, {"tlp", (void**)&c->tlp, 4 * f},
+           {"tr", (void**)&c->tr, f}, {"td", (void**)&c->td, 1}, {"tv", (void**)&c->tv, f},
+           {"tret", (void**)&c->tret, f}, {"tadv", (void**)&c->tadv, f}}};
+}
+
 int wk_create(const wk_config* cfg, int device, int n_env, uint64_t seed, wk_ctx** out) {
   if (!out) { g_create_error = "out is NULL"; return WK_ERR_ARG; }
   *out = nullptr;
@@ -420,7 +466,7 @@ int wk_create(const wk_config* cfg, int device, int n_env, uint64_t seed, wk_ctx
 
   const size_t n = (size_t)n_env, T = (size_t)x->T;
 #define ALLOC(ptr, bytes)                                                   \
-  if (hipMalloc((void**)&(ptr), (bytes)) != hipSuccess) {                  \
+  if (dev_alloc(x, &(ptr), (bytes)) != hipSuccess) {                       \
     x->err = "hipMalloc failed for " #ptr;                                  \
     return fail(WK_ERR_HIP);                                                \
   }
@@ -438,14 +484,11 @@ int wk_create(const wk_config* cfg, int device, int n_env, uint64_t seed, wk_ctx
   ALLOC(x->m, sizeof(float) * np);
   ALLOC(x->v, sizeof(float) * np);
   ALLOC(x->grad, sizeof(float) * x->slabn);
-  ALLOC(x->ts, sizeof(float) * 12 * n * T);
-  ALLOC(x->ta, sizeof(float) * 4 * n * T);
-  ALLOC(x->tlp, sizeof(float) * 4 * n * T);
-  ALLOC(x->tr, sizeof(float) * n * T);
-  ALLOC(x->tv, sizeof(float) * n * T);
-  ALLOC(x->tret, sizeof(float) * n * T);
-  ALLOC(x->tadv, sizeof(float) * n * T);
-  ALLOC(x->td, n * T);
+  for (const TrajRow& r : traj_rows(x))
+    if (dev_alloc(x, r.p, r.bytes * n * T) != hipSuccess) {
+      x->err = std::string("hipMalloc failed for x->") + r.name;
+      return fail(WK_ERR_HIP);
+    }
   if (c.ReturnsMode == 1) ALLOC(x->vlast, sizeof(float) * n);
   x->ep_cap = (uint64_t)n * T;  // one rollout's worst case: every env-step ends an episode
   x->loss_cap = 1u << 16;
@@ -531,15 +574,8 @@ int wk_destroy(wk_ctx* c) {
   for (void* p : c->xch_peers)
     if (p) (void)hipIpcCloseMemHandle(p);
   if (c->xch) (void)hipFree(c->xch);
-  if (c->xch_err) (void)hipFree(c->xch_err);
-  if (c->xch_stamps) (void)hipFree(c->xch_stamps);
-  void* bufs[] = {c->st, c->dxoff, c->mat, c->rng_t, c->W, c->Wz, c->m, c->v, c->grad, c->ts, c->ta,
-                  c->tlp, c->tr, c->tv, c->tret, c->tadv, c->td, c->partial, c->scratch, c->scratch2,
-                  c->ep_acc, c->ep_len, c->ep_scratch, c->ep_rowcnt, c->ep_count, c->ep_log,
-                  c->loss_log, c->props, c->snap, c->counts, c->order, c->order_cnt, c->pace, c->net_dev,
-                  c->vlast};
-  for (void* p : bufs)
-    if (p) (void)hipFree(p);
+  for (void** p : c->owned)
+    if (*p) (void)hipFree(*p);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
   return WK_OK;
@@ -620,6 +656,34 @@ static hipError_t launch_physics(wk_ctx* c, int mode, wk::StepArgs& A) {
   return wk::launch_env_step(mode, c->P, A, c->stream);
 }
 
+// the env-step kernels' argument block: the four walker arrays ...
+static wk::StepArgs env_args(wk_ctx* c) {
+  wk::StepArgs A{};
+  A.st = c->st; A.dxoff = c->dxoff; A.mat = c->mat; A.rng_t = c->rng_t;
+  return A;
+}
+// ... the six rows the sampling modes record, from row 0 ...
+static void set_traj(wk::StepArgs& A, float* s, float* a, float* lp, float* r, uint8_t* d, float* v) {
+  A.traj_s = s; A.traj_a = a; A.traj_lp = lp; A.traj_r = r; A.traj_d = d; A.traj_v = v;
+  A.t0 = 0;
+}
+// ... and the policy those modes run; the rows are the context's unless the caller re-points them
+static wk::StepArgs policy_args(wk_ctx* c) {
+  wk::StepArgs A = env_args(c);
+  A.W = c->W; A.Wz = c->Wz; A.lp_const = c->lp_const;
+  set_traj(A, c->ts, c->ta, c->tlp, c->tr, c->td, c->tv);
+  return A;
+}
+
+// the seam between the two kernel families: the policy / value kernel (and launch_grad_for, below)
+static hipError_t launch_policy_for(wk_ctx* c, int n, const float* obs, const int32_t* ids,
+                                    const uint32_t* steps, float* mean, float* act, float* logp, float* v) {
+  return c->general ? wk::launch_net_policy(c->P, c->net_dev, c->act_rows, c->W, c->lp_const, n, obs, ids,
+                                            steps, mean, act, logp, v, c->stream)
+                    : wk::launch_policy(c->P, c->W, c->lp_const, n, obs, ids, steps, mean, act, logp, v,
+                                        c->stream);
+}
+
 // The general networks' sampled env-steps (NetworkKernels = 1).  Per env-step: the walkers'
 // observations, the policy kernel on them (Philox step = the walker's env-step counter, as in
 // the fused kernels), then one env-step of the context's own physics kernel in its
@@ -631,21 +695,17 @@ static int net_sampled(wk_ctx* c, int k, float* d_s, float* d_a, float* d_lp, fl
   const size_t n = c->n;
   float *r_s = nullptr, *r_a = nullptr, *r_lp = nullptr, *r_v = nullptr;
   if (!d_s || !d_a || !d_lp || !d_v) {
-    if (ensure(c, &c->scratch, &c->scratch_bytes, sizeof(float) * (12 + 4 + 4 + 1) * n)) return WK_ERR_HIP;
-    r_s = (float*)c->scratch;
-    r_a = r_s + 12 * n;
-    r_lp = r_a + 4 * n;
-    r_v = r_lp + 4 * n;
+    const size_t f = sizeof(float) * n;
+    if (carve(c, &c->scratch, &c->scratch_bytes, {{&r_s, 12 * f}, {&r_a, 4 * f}, {&r_lp, 4 * f}, {&r_v, f}}))
+      return WK_ERR_HIP;
   }
   for (int j = 0; j < k; j++) {
     float* s_row = d_s ? d_s + 12 * n * j : r_s;
     float* a_row = d_a ? d_a + 4 * n * j : r_a;
     HIPCHK(c, wk::launch_get_obs(c->P, c->st, s_row, c->stream));
-    HIPCHK(c, wk::launch_net_policy(c->P, c->net_dev, c->act_rows, c->W, c->lp_const, c->n, s_row,
-                                    nullptr, c->rng_t, nullptr, a_row, d_lp ? d_lp + 4 * n * j : r_lp,
-                                    d_v ? d_v + n * j : r_v, c->stream));
-    wk::StepArgs A{};
-    A.st = c->st; A.dxoff = c->dxoff; A.mat = c->mat; A.rng_t = c->rng_t;
+    HIPCHK(c, launch_policy_for(c, c->n, s_row, nullptr, c->rng_t, nullptr, a_row,
+                                d_lp ? d_lp + 4 * n * j : r_lp, d_v ? d_v + n * j : r_v));
+    wk::StepArgs A = env_args(c);
     A.actions = a_row;
     A.obs_out = d_obs ? d_obs + 12 * n * j : nullptr;
     A.pos_out = d_pos ? d_pos + 2 * n * j : nullptr;
@@ -658,18 +718,25 @@ static int net_sampled(wk_ctx* c, int k, float* d_s, float* d_a, float* d_lp, fl
   return WK_OK;
 }
 
+// A.k_steps sampled env-steps recorded into A's rows: the fused kernel, or net_sampled
+static int sampled_steps(wk_ctx* c, wk::StepArgs& A) {
+  ProfScope ps(c, PK_PHYS, (int64_t)A.k_steps * c->n);
+  if (c->general)
+    return net_sampled(c, A.k_steps, A.traj_s, A.traj_a, A.traj_lp, A.traj_v, A.traj_r, A.traj_d, A.obs_out,
+                       A.pos_out, A.fault_out);
+  HIPCHK(c, launch_physics(c, 3, A));
+  return WK_OK;
+}
+
 static int step_impl(wk_ctx* c, const float* d_actions, int k, float* d_obs, float* d_rew,
                      uint8_t* d_done, uint32_t* d_fault, int mode, void* trace) {
   if (c->general && mode >= 2) {
     ProfScope ps(c, PK_PHYS, (int64_t)k * c->n);
     return net_sampled(c, k, nullptr, nullptr, nullptr, nullptr, d_rew, d_done, d_obs, nullptr, d_fault);
   }
-  wk::StepArgs A{};
-  A.st = c->st; A.dxoff = c->dxoff; A.mat = c->mat; A.rng_t = c->rng_t;
+  wk::StepArgs A = policy_args(c);
   A.actions = d_actions; A.obs_out = d_obs; A.rew_out = d_rew; A.done_out = d_done;
-  A.fault_out = d_fault; A.W = c->W; A.Wz = c->Wz; A.lp_const = c->lp_const;
-  A.traj_s = c->ts; A.traj_a = c->ta; A.traj_lp = c->tlp; A.traj_r = c->tr; A.traj_d = c->td;
-  A.traj_v = c->tv; A.t0 = 0;
+  A.fault_out = d_fault;
   A.trace = (wk::PairTraceDev*)trace;
   A.k_steps = k;
   ProfScope ps(c, PK_PHYS, (int64_t)k * c->n);
@@ -692,14 +759,12 @@ int wk_step(wk_ctx* c, const float* actions, int k, float* obs, float* reward, u
   const size_t b_act = actions ? sizeof(float) * 4 * n * k : 0;
   const size_t b_obs = sizeof(float) * 12 * n * k, b_rew = sizeof(float) * n * k, b_done = n * k;
   const size_t b_fault = sizeof(uint32_t) * n;
-  const size_t total = b_act + b_obs + b_rew + b_done + b_fault + 64;
-  if (ensure(c, &c->scratch2, &c->scratch2_bytes, total)) return WK_ERR_HIP;
-  char* base = (char*)c->scratch2;
-  float* d_act = actions ? (float*)base : nullptr;
-  float* d_obs = (float*)(base + b_act);
-  float* d_rew = (float*)(base + b_act + b_obs);
-  uint32_t* d_fault = (uint32_t*)(base + b_act + b_obs + b_rew);
-  uint8_t* d_done = (uint8_t*)(base + b_act + b_obs + b_rew + b_fault);
+  float *d_act, *d_obs, *d_rew;  // (d_act null without actions: no bytes)
+  uint32_t* d_fault;
+  uint8_t* d_done;
+  if (carve(c, &c->scratch2, &c->scratch2_bytes,
+            {{&d_act, b_act}, {&d_obs, b_obs}, {&d_rew, b_rew}, {&d_fault, b_fault}, {&d_done, b_done}}))
+    return WK_ERR_HIP;
   if (actions) HIPCHK(c, hipMemcpyAsync(d_act, actions, b_act, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(d_fault, 0, b_fault, c->stream));
   int r = step_impl(c, d_act, k, obs ? d_obs : nullptr, reward ? d_rew : nullptr,
@@ -789,35 +854,20 @@ int wk_step_sampled(wk_ctx* c, int k, float* states, float* actions, float* logp
   const size_t b12 = sizeof(float) * 12 * kn, b4 = sizeof(float) * 4 * kn, b1 = sizeof(float) * kn;
   const size_t b_fault = sizeof(uint32_t) * n;
   const size_t b_pos = sizeof(float) * 2 * kn;
-  const size_t total = 2 * b12 + 2 * b4 + 2 * b1 + kn + b_fault + b_pos + 9 * 64;
-  if (ensure(c, &c->scratch2, &c->scratch2_bytes, total)) return WK_ERR_HIP;
-  char* p = (char*)c->scratch2;
-  auto take = [&](size_t bytes) { char* r = p; p += (bytes + 63) & ~(size_t)63; return r; };
-  float* d_s = (float*)take(b12);
-  float* d_a = (float*)take(b4);
-  float* d_lp = (float*)take(b4);
-  float* d_v = (float*)take(b1);
-  float* d_r = (float*)take(b1);
-  float* d_o = (float*)take(b12);
-  uint32_t* d_f = (uint32_t*)take(b_fault);
-  float* d_pos = (float*)take(b_pos);
-  uint8_t* d_d = (uint8_t*)take(kn);
+  float *d_s, *d_a, *d_lp, *d_v, *d_r, *d_o, *d_pos;
+  uint32_t* d_f;
+  uint8_t* d_d;
+  if (carve(c, &c->scratch2, &c->scratch2_bytes,
+            {{&d_s, b12}, {&d_a, b4}, {&d_lp, b4}, {&d_v, b1}, {&d_r, b1}, {&d_o, b12}, {&d_f, b_fault},
+             {&d_pos, b_pos}, {&d_d, kn}}))
+    return WK_ERR_HIP;
   HIPCHK(c, hipMemsetAsync(d_f, 0, b_fault, c->stream));
-  wk::StepArgs A{};
-  A.st = c->st; A.dxoff = c->dxoff; A.mat = c->mat; A.rng_t = c->rng_t;
+  wk::StepArgs A = policy_args(c);
+  set_traj(A, d_s, d_a, d_lp, d_r, d_d, d_v);
   A.obs_out = next_obs ? d_o : nullptr; A.fault_out = d_f;
   A.pos_out = position ? d_pos : nullptr;
-  A.W = c->W; A.Wz = c->Wz; A.lp_const = c->lp_const;
-  A.traj_s = d_s; A.traj_a = d_a; A.traj_lp = d_lp; A.traj_r = d_r; A.traj_d = d_d; A.traj_v = d_v;
-  A.t0 = 0; A.k_steps = k;
-  {
-    ProfScope ps(c, PK_PHYS, (int64_t)kn);
-    if (c->general) {
-      if (int r = net_sampled(c, k, d_s, d_a, d_lp, d_v, d_r, d_d, A.obs_out, A.pos_out, d_f)) return r;
-    } else {
-      HIPCHK(c, launch_physics(c, 3, A));
-    }
-  }
+  A.k_steps = k;
+  if (int r = sampled_steps(c, A)) return r;
   if (states) HIPCHK(c, hipMemcpyAsync(states, d_s, b12, hipMemcpyDeviceToHost, c->stream));
   if (actions) HIPCHK(c, hipMemcpyAsync(actions, d_a, b4, hipMemcpyDeviceToHost, c->stream));
   if (logp) HIPCHK(c, hipMemcpyAsync(logp, d_lp, b4, hipMemcpyDeviceToHost, c->stream));
@@ -838,9 +888,9 @@ int wk_step_traced(wk_ctx* c, const float* actions, wk_pair_trace* trace) {
   const size_t n = c->n;
   const size_t b_act = sizeof(float) * 4 * n;
   const size_t b_tr = sizeof(wk_pair_trace) * n * c->cfg.Iterations;
-  if (ensure(c, &c->scratch2, &c->scratch2_bytes, b_act + b_tr + 64)) return WK_ERR_HIP;
-  float* d_act = (float*)c->scratch2;
-  void* d_tr = (char*)c->scratch2 + ((b_act + 63) / 64) * 64;
+  float* d_act;
+  void* d_tr;
+  if (carve(c, &c->scratch2, &c->scratch2_bytes, {{&d_act, b_act}, {&d_tr, b_tr}})) return WK_ERR_HIP;
   HIPCHK(c, hipMemcpyAsync(d_act, actions, b_act, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(d_tr, 0, b_tr, c->stream));
   int r = step_impl(c, d_act, 1, nullptr, nullptr, nullptr, nullptr, 1, d_tr);
@@ -1085,21 +1135,23 @@ int wk_set_scene(wk_ctx* c, const wk_prop* props, int n_props) {
   }
   S.n_props = n_props;
   S.pstride = (int)rec.size();
-  float* dev = nullptr;
+  // the new block is the context's from its allocation on: no path below has to free it
+  if (c->props_next) (void)hipFree(c->props_next);
+  c->props_next = nullptr;
   if (n_props > 0) {
     std::vector<float> all((size_t)c->n * rec.size());
     for (int e = 0; e < c->n; e++) memcpy(all.data() + (size_t)e * rec.size(), rec.data(), sizeof(float) * rec.size());
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMalloc(&dev, sizeof(float) * all.size()));
-    if (hipMemcpy(dev, all.data(), sizeof(float) * all.size(), hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipFree(dev);
+    HIPCHK(c, dev_alloc(c, &c->props_next, sizeof(float) * all.size()));
+    if (hipMemcpy(c->props_next, all.data(), sizeof(float) * all.size(), hipMemcpyHostToDevice) != hipSuccess) {
       SETERR(c, "scene upload failed");
       return WK_ERR_HIP;
     }
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (c->props) (void)hipFree(c->props);
-  c->props = dev;
+  c->props = c->props_next;
+  c->props_next = nullptr;
   c->scene = S;
   c->snap_valid = false;  // the snapshot's layout no longer matches
   c->scene_desc.assign(props, props + n_props);
@@ -1163,35 +1215,24 @@ int wk_set_adam(wk_ctx* c, const float* m, const float* v, int t) {
 static int policy_impl(wk_ctx* c, int n, const float* obs, const int32_t* ids, const uint32_t* steps,
                        float* mean, float* act, float* logp, float* v) {
   const size_t b_obs = sizeof(float) * 12 * n, b4 = sizeof(float) * 4 * n, b1 = sizeof(float) * n;
-  const size_t total = b_obs + 3 * b4 + 2 * b1 + 2 * sizeof(int32_t) * n + 256;
-  if (ensure(c, &c->scratch2, &c->scratch2_bytes, total)) return WK_ERR_HIP;
-  char* p = (char*)c->scratch2;
-  float* d_obs = (float*)p; p += b_obs;
-  float* d_mean = (float*)p; p += b4;
-  float* d_act = (float*)p; p += b4;
-  float* d_lp = (float*)p; p += b4;
-  float* d_v = (float*)p; p += b1;
-  int32_t* d_ids = (int32_t*)p; p += sizeof(int32_t) * n;
-  uint32_t* d_steps = (uint32_t*)p;
+  float *d_obs, *d_mean, *d_act, *d_lp, *d_v;
+  int32_t* d_ids;
+  uint32_t* d_steps;
+  if (carve(c, &c->scratch2, &c->scratch2_bytes,
+            {{&d_obs, b_obs}, {&d_mean, b4}, {&d_act, b4}, {&d_lp, b4}, {&d_v, b1},
+             {&d_ids, sizeof(int32_t) * n}, {&d_steps, sizeof(uint32_t) * n}}))
+    return WK_ERR_HIP;
   HIPCHK(c, hipMemcpyAsync(d_obs, obs, b_obs, hipMemcpyHostToDevice, c->stream));
   if (ids) HIPCHK(c, hipMemcpyAsync(d_ids, ids, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
   if (steps) HIPCHK(c, hipMemcpyAsync(d_steps, steps, sizeof(uint32_t) * n, hipMemcpyHostToDevice, c->stream));
-  if (c->general)
-    HIPCHK(c, wk::launch_net_policy(c->P, c->net_dev, c->act_rows, c->W, c->lp_const, n, d_obs,
-                                    ids ? d_ids : nullptr, steps ? d_steps : nullptr,
-                                    v ? nullptr : d_mean, v ? nullptr : d_act, v ? nullptr : d_lp,
-                                    v ? d_v : nullptr, c->stream));
-  else
-    HIPCHK(c, wk::launch_policy(c->P, c->W, c->lp_const, n, d_obs, ids ? d_ids : nullptr,
-                                steps ? d_steps : nullptr, v ? nullptr : d_mean, v ? nullptr : d_act,
-                                v ? nullptr : d_lp, v ? d_v : nullptr, c->stream));
-  if (v) {
-    HIPCHK(c, hipMemcpyAsync(v, d_v, b1, hipMemcpyDeviceToHost, c->stream));
-  } else {
-    if (mean) HIPCHK(c, hipMemcpyAsync(mean, d_mean, b4, hipMemcpyDeviceToHost, c->stream));
-    if (act) HIPCHK(c, hipMemcpyAsync(act, d_act, b4, hipMemcpyDeviceToHost, c->stream));
-    if (logp) HIPCHK(c, hipMemcpyAsync(logp, d_lp, b4, hipMemcpyDeviceToHost, c->stream));
-  }
+  HIPCHK(c, launch_policy_for(c, n, d_obs, ids ? d_ids : nullptr, steps ? d_steps : nullptr,
+                              v ? nullptr : d_mean, v ? nullptr : d_act, v ? nullptr : d_lp,
+                              v ? d_v : nullptr));
+  // (wk_value passes v alone, wk_policy_sample the other three)
+  if (v) HIPCHK(c, hipMemcpyAsync(v, d_v, b1, hipMemcpyDeviceToHost, c->stream));
+  if (mean) HIPCHK(c, hipMemcpyAsync(mean, d_mean, b4, hipMemcpyDeviceToHost, c->stream));
+  if (act) HIPCHK(c, hipMemcpyAsync(act, d_act, b4, hipMemcpyDeviceToHost, c->stream));
+  if (logp) HIPCHK(c, hipMemcpyAsync(logp, d_lp, b4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return WK_OK;
 }
@@ -1216,12 +1257,7 @@ static int bootstrap_values(wk_ctx* c) {
   float* obs = (float*)c->scratch;
   ProfScope ps(c, PK_RET);
   HIPCHK(c, wk::launch_get_obs(c->P, c->st, obs, c->stream));
-  if (c->general)
-    HIPCHK(c, wk::launch_net_policy(c->P, c->net_dev, c->act_rows, c->W, c->lp_const, c->n, obs, nullptr,
-                                    nullptr, nullptr, nullptr, nullptr, c->vlast, c->stream));
-  else
-    HIPCHK(c, wk::launch_policy(c->P, c->W, c->lp_const, c->n, obs, nullptr, nullptr, nullptr, nullptr,
-                                nullptr, c->vlast, c->stream));
+  HIPCHK(c, launch_policy_for(c, c->n, obs, nullptr, nullptr, nullptr, nullptr, nullptr, c->vlast));
   c->vlast_valid = true;
   return WK_OK;
 }
@@ -1252,20 +1288,9 @@ int wk_rollout(wk_ctx* c, int horizon) {
   if (!c) return WK_ERR_ARG;
   if (horizon <= 0) horizon = c->T;
   if (horizon > c->T) { SETERR(c, "horizon %d exceeds the configured Horizon %d", horizon, c->T); return WK_ERR_ARG; }
-  wk::StepArgs A{};
-  A.st = c->st; A.dxoff = c->dxoff; A.mat = c->mat; A.rng_t = c->rng_t;
-  A.W = c->W; A.Wz = c->Wz; A.lp_const = c->lp_const;
-  A.traj_s = c->ts; A.traj_a = c->ta; A.traj_lp = c->tlp; A.traj_r = c->tr; A.traj_d = c->td;
-  A.traj_v = c->tv; A.t0 = 0; A.k_steps = horizon;
-  {
-    ProfScope ps(c, PK_PHYS, (int64_t)horizon * c->n);
-    if (c->general) {
-      if (int r = net_sampled(c, horizon, c->ts, c->ta, c->tlp, c->tv, c->tr, c->td, nullptr, nullptr, nullptr))
-        return r;
-    } else {
-      HIPCHK(c, launch_physics(c, 3, A));
-    }
-  }
+  wk::StepArgs A = policy_args(c);
+  A.k_steps = horizon;
+  if (int r = sampled_steps(c, A)) return r;
   c->T_valid = horizon;
   if (c->collect) {
     wk::EpisodeArgs e{c->n, horizon, c->cfg.EnvOffset, c->rollout_steps, c->tr, c->td, c->ep_acc,
@@ -1310,14 +1335,10 @@ int wk_get_trajectory(wk_ctx* c, float* s, float* a, float* lp, float* r, uint8_
   if (!c) return WK_ERR_ARG;
   const size_t cnt = (size_t)c->n * c->T_valid;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (s) HIPCHK(c, hipMemcpy(s, c->ts, sizeof(float) * 12 * cnt, hipMemcpyDeviceToHost));
-  if (a) HIPCHK(c, hipMemcpy(a, c->ta, sizeof(float) * 4 * cnt, hipMemcpyDeviceToHost));
-  if (lp) HIPCHK(c, hipMemcpy(lp, c->tlp, sizeof(float) * 4 * cnt, hipMemcpyDeviceToHost));
-  if (r) HIPCHK(c, hipMemcpy(r, c->tr, sizeof(float) * cnt, hipMemcpyDeviceToHost));
-  if (d) HIPCHK(c, hipMemcpy(d, c->td, cnt, hipMemcpyDeviceToHost));
-  if (v) HIPCHK(c, hipMemcpy(v, c->tv, sizeof(float) * cnt, hipMemcpyDeviceToHost));
-  if (ret) HIPCHK(c, hipMemcpy(ret, c->tret, sizeof(float) * cnt, hipMemcpyDeviceToHost));
-  if (adv) HIPCHK(c, hipMemcpy(adv, c->tadv, sizeof(float) * cnt, hipMemcpyDeviceToHost));
+  void* const host[8] = {s, a, lp, r, d, v, ret, adv};
+  const auto rows = traj_rows(c);
+  for (size_t i = 0; i < rows.size(); i++)
+    if (host[i]) HIPCHK(c, hipMemcpy(host[i], *rows[i].p, rows[i].bytes * cnt, hipMemcpyDeviceToHost));
   return WK_OK;
 }
 
@@ -1327,12 +1348,10 @@ int wk_set_trajectory(wk_ctx* c, int horizon, const float* s, const float* a, co
   if (!c || horizon <= 0 || horizon > c->T || !s || !a || !lp || !r || !d || !v) return WK_ERR_ARG;
   const size_t cnt = (size_t)c->n * horizon;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(c->ts, s, sizeof(float) * 12 * cnt, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->ta, a, sizeof(float) * 4 * cnt, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->tlp, lp, sizeof(float) * 4 * cnt, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->tr, r, sizeof(float) * cnt, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->td, d, cnt, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->tv, v, sizeof(float) * cnt, hipMemcpyHostToDevice));
+  const void* const host[6] = {s, a, lp, r, d, v};
+  const auto rows = traj_rows(c);
+  for (size_t i = 0; i < 6; i++)
+    HIPCHK(c, hipMemcpy(*rows[i].p, host[i], rows[i].bytes * cnt, hipMemcpyHostToDevice));
   c->T_valid = horizon;
   c->returns_valid = false;
   c->vlast_valid = false;
@@ -1374,18 +1393,29 @@ static uint64_t* xch_stamp_slot(wk_ctx* c) {
   return c->xch_stamps + (size_t)slot * wk::xch_blocks() * wk::XCH_POINTS;
 }
 
-// one minibatch: gradient kernel -> ordered block reduction -> [RCCL all-reduce] -> Adam
-// wpb == 0: the matrix-core kernel (wk_ppo_mfma.hip); wpb >= 1: the lane-per-neuron
-// kernel (wk_ppo.hip; wpb == 1 visits the samples in minibatch order)
-static int ensure_partial(wk_ctx* c, size_t need) {
-  if (c->partial_floats < need) {
-    if (c->partial) (void)hipFree(c->partial);
-    c->partial = nullptr;
-    c->partial_floats = 0;
-    HIPCHK(c, hipMalloc((void**)&c->partial, sizeof(float) * need));
-    c->partial_floats = need;
+// How many block slabs of what size g's gradient kernel (*gi) writes, and g.partial = c->partial
+// sized for them.  Built-in kernels: nblocks slabs of SLAB floats followed by the stage-1 group
+// sums of the ordered reduction; general kernels (always k_net_grad): nblocks slabs of slabn floats.
+static int grad_slabs(wk_ctx* c, wk::GradArgs& g, int wpb, int* gi, int* nblocks) {
+  size_t floats;
+  *gi = wk::grad_impl_for(c->grad_impl, g.samples);
+  if (c->general) {
+    *nblocks = wk::net_grad_blocks(g.samples);
+    floats = (size_t)*nblocks * c->slabn;
+  } else {
+    *nblocks = wpb == 0 ? wk::ppo_grad_mfma_blocks(g.samples, *gi)
+                        : (g.samples + wpb * g.spw - 1) / (wpb * g.spw);
+    floats = ((size_t)*nblocks + wk::grad_reduce_groups(*nblocks)) * wk::SLAB;
   }
+  if (ensure(c, &c->partial, &c->partial_bytes, sizeof(float) * floats)) return WK_ERR_HIP;
+  g.partial = c->partial;
   return WK_OK;
+}
+
+// the kernel family's matrix-core gradient kernel (the seam's other half, see launch_policy_for)
+static hipError_t launch_grad_for(wk_ctx* c, const wk::GradArgs& g, int nblocks, int gi) {
+  return c->general ? wk::launch_net_grad(g, c->net_dev, c->act_rows, c->np, c->stream)
+                    : wk::launch_ppo_grad_mfma(g, nblocks, gi, c->stream);
 }
 
 static wk::AdamArgs adam_args(wk_ctx* c) {  // advances the step count
@@ -1404,43 +1434,30 @@ static wk::AdamArgs adam_args(wk_ctx* c) {  // advances the step count
   return a;
 }
 
-// the general networks' minibatch: k_net_grad, then the ordered sum of its block slabs with
-// Adam in the same launch (one GPU: the exchanges refuse such a context)
-static int net_minibatch(wk_ctx* c, wk::GradArgs g, int apply_adam) {
-  const int nblocks = wk::net_grad_blocks(g.samples);
-  if (int r = ensure_partial(c, (size_t)nblocks * c->slabn)) return r;
-  g.partial = c->partial;
+// one minibatch: gradient kernel -> ordered block reduction -> [RCCL all-reduce] -> Adam
+// wpb == 0: the matrix-core kernel (wk_ppo_mfma.hip); wpb >= 1: the lane-per-neuron
+// kernel (wk_ppo.hip; wpb == 1 visits the samples in minibatch order)
+static int minibatch(wk_ctx* c, wk::GradArgs g, int wpb, int apply_adam) {
+  int gi, nblocks;
+  if (int r = grad_slabs(c, g, wpb, &gi, &nblocks)) return r;
   wk::AdamArgs a{};
   if (apply_adam) a = adam_args(c);
   {
     ProfScope ps(c, PK_GRAD, 0, 2);
-    HIPCHK(c, wk::launch_net_grad(g, c->net_dev, c->act_rows, c->np, c->stream));
+    HIPCHK(c, wpb == 0 || c->general ? launch_grad_for(c, g, nblocks, gi)
+                                     : wk::launch_ppo_grad(g, wpb, nblocks, c->stream));
   }
-  ProfScope ps(c, PK_REDUCE, 0, 2);
-  HIPCHK(c, wk::launch_net_reduce(c->partial, nblocks, c->np, c->grad, a, c->stream));
-  return WK_OK;
-}
-
-static int minibatch(wk_ctx* c, wk::GradArgs g, int wpb, int apply_adam) {
-  if (c->general) return net_minibatch(c, g, apply_adam);
-  const int gi = wk::grad_impl_for(c->grad_impl, g.samples);
-  const int nblocks = wpb == 0 ? wk::ppo_grad_mfma_blocks(g.samples, gi)
-                               : (g.samples + wpb * g.spw - 1) / (wpb * g.spw);
-  // block slabs followed by the stage-1 group sums of the ordered reduction
-  const size_t need = ((size_t)nblocks + wk::grad_reduce_groups(nblocks)) * wk::SLAB;
-  if (int r = ensure_partial(c, need)) return r;
-  g.partial = c->partial;
-  wk::AdamArgs a{};
-  if (apply_adam) a = adam_args(c);
+  // the general networks: the ordered sum of k_net_grad's block slabs with Adam in the same
+  // launch (one GPU: the exchanges refuse such a context)
+  if (c->general) {
+    ProfScope ps(c, PK_REDUCE, 0, 2);
+    HIPCHK(c, wk::launch_net_reduce(c->partial, nblocks, c->np, c->grad, a, c->stream));
+    return WK_OK;
+  }
   float* part2 = c->partial + (size_t)nblocks * wk::SLAB;
   // with a communicator (any size, also one rank) the collective path runs: reduction,
   // RCCL all-reduce, Adam -- a single-GPU test then covers the multi-GPU sequence
   const bool multi = c->comm != nullptr || c->host_ar != nullptr || c->ipc;
-  {
-    ProfScope ps(c, PK_GRAD, 0, 2);
-    HIPCHK(c, wpb == 0 ? wk::launch_ppo_grad_mfma(g, nblocks, gi, c->stream)
-                       : wk::launch_ppo_grad(g, wpb, nblocks, c->stream));
-  }
   // reduction, exchange and Adam in one launch (k_reduce_xch_adam); a gradient-only call
   // (apply_adam 0: a.W == null) runs the exchange alone, so on every kind of context the
   // returned gradient is the sum over the ranks
@@ -1545,6 +1562,17 @@ static wk::GradArgs grad_base(wk_ctx* c) {
   return g;
 }
 
+// minibatches of M keyed samples out of the context's trajectory (the caller sets pk and base)
+static wk::GradArgs traj_grad_args(wk_ctx* c, int M, float b_div) {
+  wk::GradArgs g = grad_base(c);
+  g.states = c->ts; g.actions = c->ta; g.logp_old = c->tlp; g.returns = c->tret; g.adv = c->tadv;
+  g.pool = (uint32_t)((size_t)c->n * c->T_valid);
+  g.use_perm = 1;
+  g.samples = M;
+  g.b_div = b_div;
+  return g;
+}
+
 static int ppo_update_impl(wk_ctx* c, const wk_ppo_args* args);
 // The gradient kernel alone, `reps` back-to-back launches on minibatch 0 of the keyed sequence
 // (update 0, epoch 0) of the current trajectory, between one HIP-event pair on the context's
@@ -1600,44 +1628,34 @@ int wk_time_gradient_ex(wk_ctx* c, int minibatch, int reps, int flags, double* m
   const int M = minibatch > 0 ? minibatch : c->cfg.Minibatch;
   const uint32_t pool = (uint32_t)((size_t)c->n * c->T_valid);
   if ((uint32_t)M > pool) { SETERR(c, "minibatch %d larger than the pool %u", M, pool); return WK_ERR_ARG; }
-  wk::GradArgs g = grad_base(c);
-  g.states = c->ts; g.actions = c->ta; g.logp_old = c->tlp; g.returns = c->tret; g.adv = c->tadv;
-  g.pool = pool;
-  g.use_perm = 1;
-  g.samples = M;
-  g.b_div = (float)(c->cfg.MinibatchGlobal > 0 ? c->cfg.MinibatchGlobal : M);
+  wk::GradArgs g = traj_grad_args(c, M, (float)(c->cfg.MinibatchGlobal > 0 ? c->cfg.MinibatchGlobal : M));
   g.pk = wk::perm_key(c->seed, 0u, 0u, pool);
-  g.base = 0;
-  const int gi = wk::grad_impl_for(c->grad_impl, M);
-  const int nblocks = c->general ? wk::net_grad_blocks(M) : wk::ppo_grad_mfma_blocks(M, gi);
-  const size_t need = c->general ? (size_t)nblocks * c->slabn
-                                 : ((size_t)nblocks + wk::grad_reduce_groups(nblocks)) * wk::SLAB;
-  if (int r = ensure_partial(c, need)) return r;
-  g.partial = c->partial;
-  auto launch = [&]() {
-    return c->general ? wk::launch_net_grad(g, c->net_dev, c->act_rows, c->np, c->stream)
-                      : wk::launch_ppo_grad_mfma(g, nblocks, gi, c->stream);
-  };
-  HIPCHK(c, launch());  // warm
+  int gi, nblocks;
+  if (int r = grad_slabs(c, g, 0, &gi, &nblocks)) return r;
+  HIPCHK(c, launch_grad_for(c, g, nblocks, gi));  // warm
   // flags & 1: an event pair around EVERY launch (as profile level 2 times the update's
   // launches), the elapsed times summed -- the burst's per-launch event overhead is the
   // difference to one pair around the whole burst
   const int npairs = (flags & 1) ? reps : 1;
-  std::vector<hipEvent_t> ev(2 * (size_t)npairs, nullptr);
-  for (auto& e : ev) HIPCHK(c, hipEventCreate(&e));
+  // the events stay in the context's pool (nothing below draws from it): no path has to free them
+  while (c->pool.size() < 2 * (size_t)npairs) {
+    hipEvent_t e;
+    HIPCHK(c, hipEventCreate(&e));
+    c->pool.push_back(e);
+  }
+  const hipEvent_t* ev = c->pool.data() + c->pool.size() - 2 * (size_t)npairs;
   for (int i = 0; i < reps; i++) {
     if ((flags & 1) || i == 0) HIPCHK(c, hipEventRecord(ev[2 * ((flags & 1) ? i : 0)], c->stream));
-    HIPCHK(c, launch());
+    HIPCHK(c, launch_grad_for(c, g, nblocks, gi));
     if ((flags & 1) || i == reps - 1) HIPCHK(c, hipEventRecord(ev[2 * ((flags & 1) ? i : 0) + 1], c->stream));
   }
-  HIPCHK(c, hipEventSynchronize(ev.back()));
+  HIPCHK(c, hipEventSynchronize(ev[2 * npairs - 1]));
   double total = 0.0;
   for (int i = 0; i < npairs; i++) {
     float ms = 0.0f;
     HIPCHK(c, hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]));
     total += ms;
   }
-  for (auto& e : ev) (void)hipEventDestroy(e);
   *ms_per_launch = total / reps;
   return WK_OK;
 }
@@ -1685,14 +1703,7 @@ static int ppo_update_impl(wk_ctx* c, const wk_ppo_args* args) {
   const int nmb = (int)(pool / (uint32_t)M);  // remainder dropped (PPOAgent.cs:506)
   if (nmb <= 0) { SETERR(c, "minibatch %d larger than the pool %u", M, pool); return WK_ERR_ARG; }
   const int wpb = 0;  // matrix cores
-  const int spw = 0;
-  wk::GradArgs g = grad_base(c);
-  g.states = c->ts; g.actions = c->ta; g.logp_old = c->tlp; g.returns = c->tret; g.adv = c->tadv;
-  g.pool = pool;
-  g.use_perm = 1;
-  g.samples = M;
-  g.spw = spw;
-  g.b_div = (float)Mg;
+  wk::GradArgs g = traj_grad_args(c, M, (float)Mg);
   for (int e = 0; e < epochs; e++) {
     g.pk = wk::perm_key(c->seed, update, (uint32_t)e, pool);
     for (int j = 0; j < nmb; j++) {
@@ -1709,14 +1720,10 @@ static int batch_impl(wk_ctx* c, int wpb, int B, float b_div, const float* s, co
                       float* grads_out, int apply_adam, int* skipped) {
   if (!c || B <= 0 || !s || !a || !lpo || !ret || !adv) return WK_ERR_ARG;
   const size_t bs = sizeof(float) * B;
-  const size_t total = bs * (12 + 4 + 4 + 1 + 1) + 256;
-  if (ensure(c, &c->scratch2, &c->scratch2_bytes, total)) return WK_ERR_HIP;
-  char* p = (char*)c->scratch2;
-  float* d_s = (float*)p; p += bs * 12;
-  float* d_a = (float*)p; p += bs * 4;
-  float* d_l = (float*)p; p += bs * 4;
-  float* d_r = (float*)p; p += bs;
-  float* d_v = (float*)p;
+  float *d_s, *d_a, *d_l, *d_r, *d_v;
+  if (carve(c, &c->scratch2, &c->scratch2_bytes,
+            {{&d_s, bs * 12}, {&d_a, bs * 4}, {&d_l, bs * 4}, {&d_r, bs}, {&d_v, bs}}))
+    return WK_ERR_HIP;
   HIPCHK(c, hipMemcpyAsync(d_s, s, bs * 12, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d_a, a, bs * 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d_l, lpo, bs * 4, hipMemcpyHostToDevice, c->stream));
@@ -1760,6 +1767,12 @@ int wk_minibatch_gradient(wk_ctx* c, int B, float b_div, const float* s, const f
   return batch_impl(c, 0, B, b_div, s, a, lpo, ret, adv, cd, ad, grads_out, 0, skipped);
 }
 
+static int refuse_general_comm(wk_ctx* c) {
+  if (!c->general) return WK_OK;
+  SETERR(c, "the multi-GPU gradient exchange serves the built-in kernels only (NetworkKernels = 0)");
+  return WK_ERR_CONFIG;
+}
+
 int wk_comm_unique_id(uint8_t* id) {
   if (!id) return WK_ERR_ARG;
   static_assert(sizeof(ncclUniqueId) == 128, "nccl id size");
@@ -1773,10 +1786,7 @@ int wk_comm_unique_id(uint8_t* id) {
 int wk_comm_init(wk_ctx* c, int rank, int nranks, const uint8_t* id) {
   DevGuard dg_(c);
   if (!c || !id || nranks <= 0 || rank < 0 || rank >= nranks) return WK_ERR_ARG;
-  if (c->general) {
-    SETERR(c, "the multi-GPU gradient exchange serves the built-in kernels only (NetworkKernels = 0)");
-    return WK_ERR_CONFIG;
-  }
+  if (int r = refuse_general_comm(c)) return r;
   if (c->host_ar) { SETERR(c, "the context already has a host all-reduce"); return WK_ERR_STATE; }
   HIPCHK(c, hipSetDevice(c->device));
   ncclUniqueId u;
@@ -1791,10 +1801,7 @@ int wk_comm_init(wk_ctx* c, int rank, int nranks, const uint8_t* id) {
 int wk_comm_init_host(wk_ctx* c, int rank, int nranks, wk_host_allreduce_fn fn, void* user) {
   DevGuard dg_(c);
   if (!c || !fn || nranks <= 0 || rank < 0 || rank >= nranks) return WK_ERR_ARG;
-  if (c->general) {
-    SETERR(c, "the multi-GPU gradient exchange serves the built-in kernels only (NetworkKernels = 0)");
-    return WK_ERR_CONFIG;
-  }
+  if (int r = refuse_general_comm(c)) return r;
   if (c->comm) { SETERR(c, "the context already has an RCCL communicator"); return WK_ERR_STATE; }
   c->host_ar = fn;
   c->host_ar_user = user;
@@ -1811,10 +1818,7 @@ static_assert(sizeof(hipIpcMemHandle_t) == kIpcDevOff && WK_IPC_HANDLE_BYTES == 
 int wk_comm_ipc_handle(wk_ctx* c, uint8_t* handle) {
   DevGuard dg_(c);
   if (!c || !handle) return WK_ERR_ARG;
-  if (c->general) {
-    SETERR(c, "the multi-GPU gradient exchange serves the built-in kernels only (NetworkKernels = 0)");
-    return WK_ERR_CONFIG;
-  }
+  if (int r = refuse_general_comm(c)) return r;
   if (!c->xch) {
     // uncached (MTYPE UC) device memory: the peers read it over xGMI and this GPU writes it
     // through no cache; coarse-grained hipMalloc memory is the fallback where the driver cannot
@@ -1832,7 +1836,7 @@ int wk_comm_ipc_handle(wk_ctx* c, uint8_t* handle) {
       c->xch_uncached = true;
     }
     HIPCHK(c, hipMemset(c->xch, 0, bytes));
-    HIPCHK(c, hipMalloc((void**)&c->xch_err, 2 * sizeof(uint32_t)));
+    HIPCHK(c, dev_alloc(c, &c->xch_err, 2 * sizeof(uint32_t)));
     HIPCHK(c, hipMemset(c->xch_err, 0, 2 * sizeof(uint32_t)));
   }
   hipIpcMemHandle_t h;
@@ -1847,10 +1851,7 @@ int wk_comm_ipc_handle(wk_ctx* c, uint8_t* handle) {
 int wk_comm_init_ipc(wk_ctx* c, int rank, int nranks, const uint8_t* handles) {
   DevGuard dg_(c);
   if (!c || !handles || nranks <= 0 || rank < 0 || rank >= nranks) return WK_ERR_ARG;
-  if (c->general) {
-    SETERR(c, "the multi-GPU gradient exchange serves the built-in kernels only (NetworkKernels = 0)");
-    return WK_ERR_CONFIG;
-  }
+  if (int r = refuse_general_comm(c)) return r;
   if (nranks > wk::XCH_MAX_RANKS) { SETERR(c, "the IPC exchange spans at most %d ranks", (int)wk::XCH_MAX_RANKS); return WK_ERR_ARG; }
   if (c->comm || c->host_ar || c->ipc) { SETERR(c, "the context already has an all-reduce"); return WK_ERR_STATE; }
   if (!c->xch) { SETERR(c, "wk_comm_ipc_handle first"); return WK_ERR_STATE; }
@@ -1921,7 +1922,7 @@ int wk_comm_xch_profile(wk_ctx* c, int minibatches) {
   c->xch_stamp_launches = 0;
   if (minibatches == 0) return WK_OK;
   const size_t bytes = sizeof(uint64_t) * (size_t)minibatches * wk::xch_blocks() * wk::XCH_POINTS;
-  HIPCHK(c, hipMalloc((void**)&c->xch_stamps, bytes));
+  HIPCHK(c, dev_alloc(c, &c->xch_stamps, bytes));
   HIPCHK(c, hipMemset(c->xch_stamps, 0, bytes));
   c->xch_stamp_cap = minibatches;
   return WK_OK;
@@ -1987,10 +1988,9 @@ int wk_count_events(wk_ctx* c, int k, uint64_t* counts) {
   if (k > c->T_valid) { SETERR(c, "count replay of %d env-steps, the trajectory holds %d", k, c->T_valid); return WK_ERR_STATE; }
   if (c->scene.n_props > 0) { SETERR(c, "the counting replay runs without scene props"); return WK_ERR_CONFIG; }
   static_assert(WK_NEV == wk::NEV, "event counters");
-  if (!c->counts) HIPCHK(c, hipMalloc((void**)&c->counts, sizeof(unsigned long long) * wk::NEV));
+  if (!c->counts) HIPCHK(c, dev_alloc(c, &c->counts, sizeof(unsigned long long) * wk::NEV));
   HIPCHK(c, hipMemsetAsync(c->counts, 0, sizeof(unsigned long long) * wk::NEV, c->stream));
-  wk::StepArgs A{};
-  A.st = c->st; A.dxoff = c->dxoff; A.mat = c->mat; A.rng_t = c->rng_t;
+  wk::StepArgs A = env_args(c);
   A.actions = c->ta; A.k_steps = k; A.counts = c->counts;
   HIPCHK(c, wk::launch_env_step(4, c->P, A, c->stream));
   unsigned long long h[wk::NEV];
@@ -2004,7 +2004,6 @@ int wk_snapshot(wk_ctx* c, int op) {
   DevGuard dg_(c);
   if (!c || op < 0 || op > 1) return WK_ERR_ARG;
   const size_t n = c->n;
-  struct Seg { void* p; size_t bytes; };
   const Seg segs[] = {
       {c->st, sizeof(float) * wk::NSTATE * n}, {c->rng_t, sizeof(uint32_t) * n},
       {c->W, sizeof(float) * c->np}, {c->Wz, c->Wz ? sizeof(float) * wk::mfma_image_floats() : 0},
@@ -2015,12 +2014,7 @@ int wk_snapshot(wk_ctx* c, int op) {
   size_t total = 0;
   for (const Seg& g : segs) total += (g.bytes + 255) & ~(size_t)255;
   if (op == 0) {
-    if (c->snap_bytes < total) {
-      if (c->snap) (void)hipFree(c->snap);
-      c->snap = nullptr; c->snap_bytes = 0;
-      HIPCHK(c, hipMalloc(&c->snap, total));
-      c->snap_bytes = total;
-    }
+    if (ensure(c, &c->snap, &c->snap_bytes, total)) return WK_ERR_HIP;
     c->snap_adam_t = c->adam_t;
     c->snap_rollout_steps = c->rollout_steps;
     c->snap_loss_count = c->loss_count;
@@ -2200,9 +2194,22 @@ const uint32_t kCkptVersion = 4;
 // uint32 lengths and the critic and actor strings, and nparam parameters of that network.  A
 // built-in context still writes version 4, byte for byte as before
 const uint32_t kCkptVersionNet = 5;
-size_t ckpt_bytes(size_t n, size_t np) {
-  return sizeof(CkptHeader) + sizeof(float) * (3 * np + n * wk::NSTATE + 2 * n) +
-         sizeof(int32_t) * n + sizeof(double) * n + sizeof(int32_t) * n;
+// The file's fixed sections, in file order, between its variable head (header, CkptExt, the
+// version-5 network section) and its scene section: the only place that knows the order
+std::array<Seg, 9> ckpt_sections(const wk_ctx* c) {
+  const size_t n = c->n, wbytes = sizeof(float) * c->np;
+  return {{{c->W, wbytes}, {c->m, wbytes}, {c->v, wbytes}, {c->st, sizeof(float) * wk::NSTATE * n},
+           {c->rng_t, sizeof(uint32_t) * n}, {c->dxoff, sizeof(float) * n}, {c->mat, sizeof(int32_t) * n},
+           {c->ep_acc, sizeof(double) * n}, {c->ep_len, sizeof(int32_t) * n}}};
+}
+// the bytes of the sections before the one held in `until` (null: of all of them)
+size_t ckpt_offset(const wk_ctx* c, const void* until) {
+  size_t off = 0;
+  for (const Seg& g : ckpt_sections(c)) {
+    if (g.p == until) break;
+    off += g.bytes;
+  }
+  return off;
 }
 }  // namespace
 
@@ -2305,7 +2312,6 @@ int wk_checkpoint_save(wk_ctx* c, const char* path) {
   DevGuard dg_(c);
   if (!c || !path) return WK_ERR_ARG;
   const size_t n = c->n;
-  const size_t wbytes = sizeof(float) * c->np;
   CkptHeader h{kCkptMagic, c->general ? kCkptVersionNet : kCkptVersion, (uint32_t)n, (uint32_t)wk::NSTATE,
                (uint32_t)c->np, (uint32_t)c->adam_t, c->seed, c->cfg.EnvOffset, c->cfg.Iterations,
                c->cfg.MaxTimesteps, c->rollout_steps};
@@ -2313,21 +2319,16 @@ int wk_checkpoint_save(wk_ctx* c, const char* path) {
   const size_t scene_bytes = sizeof(int32_t) + sizeof(wk_prop) * np + sizeof(float) * n * c->scene.pstride;
   const CkptExt ext{c->cfg.RoughFloor, c->P.lanes, c->general ? 1 : 0, 0};
   const std::string nets = c->general ? net_section(c) : std::string();
-  std::vector<char> buf(ckpt_bytes(n, c->np) + sizeof ext + nets.size() + scene_bytes);
+  std::vector<char> buf(sizeof h + sizeof ext + nets.size() + ckpt_offset(c, nullptr) + scene_bytes);
   char* q = buf.data();
   memcpy(q, &h, sizeof h); q += sizeof h;
   memcpy(q, &ext, sizeof ext); q += sizeof ext;
   memcpy(q, nets.data(), nets.size()); q += nets.size();
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(q, c->W, wbytes, hipMemcpyDeviceToHost)); q += wbytes;
-  HIPCHK(c, hipMemcpy(q, c->m, wbytes, hipMemcpyDeviceToHost)); q += wbytes;
-  HIPCHK(c, hipMemcpy(q, c->v, wbytes, hipMemcpyDeviceToHost)); q += wbytes;
-  HIPCHK(c, hipMemcpy(q, c->st, sizeof(float) * n * wk::NSTATE, hipMemcpyDeviceToHost)); q += sizeof(float) * n * wk::NSTATE;
-  HIPCHK(c, hipMemcpy(q, c->rng_t, sizeof(uint32_t) * n, hipMemcpyDeviceToHost)); q += sizeof(uint32_t) * n;
-  HIPCHK(c, hipMemcpy(q, c->dxoff, sizeof(float) * n, hipMemcpyDeviceToHost)); q += sizeof(float) * n;
-  HIPCHK(c, hipMemcpy(q, c->mat, sizeof(int32_t) * n, hipMemcpyDeviceToHost)); q += sizeof(int32_t) * n;
-  HIPCHK(c, hipMemcpy(q, c->ep_acc, sizeof(double) * n, hipMemcpyDeviceToHost)); q += sizeof(double) * n;
-  HIPCHK(c, hipMemcpy(q, c->ep_len, sizeof(int32_t) * n, hipMemcpyDeviceToHost)); q += sizeof(int32_t) * n;
+  for (const Seg& g : ckpt_sections(c)) {
+    HIPCHK(c, hipMemcpy(q, g.p, g.bytes, hipMemcpyDeviceToHost));
+    q += g.bytes;
+  }
   const int32_t np32 = np;
   memcpy(q, &np32, sizeof np32); q += sizeof np32;
   if (np > 0) {
@@ -2384,8 +2385,7 @@ int wk_checkpoint_load(wk_ctx* c, const char* path) {
     }
     ext_bytes += mine.size();
   }
-  const size_t wbytes = sizeof(float) * c->np;
-  size_t need = ckpt_bytes(n, c->np) + ext_bytes + sizeof(int32_t);
+  size_t need = sizeof h + ext_bytes + ckpt_offset(c, nullptr) + sizeof(int32_t);
   int32_t np = 0;
   std::vector<wk_prop> desc;
   if (data.size() >= need) {
@@ -2427,7 +2427,7 @@ int wk_checkpoint_load(wk_ctx* c, const char* path) {
   }
   {  // the walker records keep rigid template poles, checked before any write
     std::vector<float> rec(n * wk::NSTATE);
-    memcpy(rec.data(), data.data() + sizeof h + ext_bytes + 3 * wbytes,
+    memcpy(rec.data(), data.data() + sizeof h + ext_bytes + ckpt_offset(c, c->st),
            sizeof(float) * rec.size());
     if (int r = check_state_or_fail(c, rec.data())) return r;
   }
@@ -2436,21 +2436,15 @@ int wk_checkpoint_load(wk_ctx* c, const char* path) {
   if (int r = wk_set_scene(c, desc.data(), (int)desc.size()); r != WK_OK) return r;
   const char* q = data.data() + sizeof h + ext_bytes;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(c->W, q, wbytes, hipMemcpyHostToDevice)); q += wbytes;
-  HIPCHK(c, hipMemcpy(c->m, q, wbytes, hipMemcpyHostToDevice)); q += wbytes;
-  HIPCHK(c, hipMemcpy(c->v, q, wbytes, hipMemcpyHostToDevice)); q += wbytes;
-  HIPCHK(c, hipMemcpy(c->st, q, sizeof(float) * n * wk::NSTATE, hipMemcpyHostToDevice)); q += sizeof(float) * n * wk::NSTATE;
-  HIPCHK(c, hipMemcpy(c->rng_t, q, sizeof(uint32_t) * n, hipMemcpyHostToDevice)); q += sizeof(uint32_t) * n;
-  HIPCHK(c, hipMemcpy(c->dxoff, q, sizeof(float) * n, hipMemcpyHostToDevice));
-  {
-    std::vector<float> dxh(n);
-    std::memcpy(dxh.data(), q, sizeof(float) * n);
-    HIPCHK(c, rough_order_upload(c, dxh.data()));
+  for (const Seg& g : ckpt_sections(c)) {
+    HIPCHK(c, hipMemcpy(g.p, q, g.bytes, hipMemcpyHostToDevice));
+    if (g.p == c->dxoff) {  // the offsets also set the rough floor's lane order
+      std::vector<float> dxh(n);
+      std::memcpy(dxh.data(), q, sizeof(float) * n);
+      HIPCHK(c, rough_order_upload(c, dxh.data()));
+    }
+    q += g.bytes;
   }
-  q += sizeof(float) * n;
-  HIPCHK(c, hipMemcpy(c->mat, q, sizeof(int32_t) * n, hipMemcpyHostToDevice)); q += sizeof(int32_t) * n;
-  HIPCHK(c, hipMemcpy(c->ep_acc, q, sizeof(double) * n, hipMemcpyHostToDevice)); q += sizeof(double) * n;
-  HIPCHK(c, hipMemcpy(c->ep_len, q, sizeof(int32_t) * n, hipMemcpyHostToDevice)); q += sizeof(int32_t) * n;
   if (np > 0) {
     q += sizeof(int32_t) + sizeof(wk_prop) * np;
     HIPCHK(c, hipMemcpy(c->props, q, sizeof(float) * n * c->scene.pstride, hipMemcpyHostToDevice));

@@ -126,6 +126,57 @@ def test_count_events_rough_floor(wk, orc):
     assert ev["aabb_lf"] > 0 and ev["sat_lf"] > 0 and ev["resets"] > 0
 
 
+def test_create_destroy_releases_device_memory(wk):
+    """twenty contexts created and closed -- 64 and 4,096 walkers, built-in and general networks,
+    ReturnsMode 1, a scene prop, and contexts that grew every lazily allocated buffer (counting
+    replay, snapshot, host step, policy sample, gradient timing) -- leave the device's free memory
+    within one context's footprint of where it was.  The bound is the [T][n] trajectory rows of
+    the 4,096-walker context alone (a lower bound of its footprint; the runtime's pool makes exact
+    equality unreliable); one buffer leaked per context would add up over the rounds"""
+    torch = pytest.importorskip("torch")
+    big, T = 4096, 64  # Horizon default
+    footprint = big * T * (4 * (12 + 4 + 4 + 1 + 1 + 1 + 1) + 1)
+    obs = np.zeros((32, 12), F)
+
+    def busy(e):
+        e.rollout(4)
+        e.snapshot()
+        e.step(k=1)
+        e.step(np.zeros((1, e.n, 4), F), k=1)
+        e.policy_sample(obs)
+        e.time_gradient(minibatch=64, reps=2)
+        e.restore()
+
+    def busy_counting(e):
+        busy(e)
+        e.count_events(4)
+
+    shapes = [(64, {}, None),
+              (big, dict(NetworkKernels=1), None),
+              (big, dict(ReturnsMode=1), None),
+              (64, dict(NetworkKernels=1, ReturnsMode=1), busy),
+              (64, dict(LanesPerWalker=1), lambda e: e.set_scene([wk.make_prop(cx=300.0, cy=700.0)])),
+              (big, {}, busy_counting),
+              (big, dict(NetworkKernels=1), busy)]
+
+    def run(i):
+        n, cfg, use = shapes[i % len(shapes)]
+        with wk.Engine(n, seed=SEED + i, **cfg) as e:
+            if use:
+                use(e)
+
+    for i in range(len(shapes)):  # code objects and the runtime's own pools, before the reading
+        run(i)
+    torch.cuda.synchronize()
+    free0, _ = torch.cuda.mem_get_info()
+    for i in range(20):
+        run(i)
+    torch.cuda.synchronize()
+    free1, _ = torch.cuda.mem_get_info()
+    print(f"free before {free0} after {free1} delta {free0 - free1} bound {footprint}")
+    assert abs(free0 - free1) <= footprint
+
+
 def test_snapshot_restore_repeats_an_iteration(wk):
     n, T = 1024, 8
     eng = wk.Engine(n, seed=SEED, Horizon=T, Minibatch=1024, RandomizeStart=1)

@@ -178,6 +178,81 @@ def test_rejected_checkpoint_leaves_context_unchanged(wk, tmp_path):
         dst.close()
 
 
+CKPT_NETS = ("Input |8| (TanH) |1| Output", "Input |8| (TanH) |4| (TanH) Output")
+
+
+@pytest.mark.parametrize("general", [False, True])
+def test_checkpoint_byte_layout(wk, tmp_path, general):
+    """the saved file parsed by its documented layout, not through checkpoint_load: 48-byte header,
+    16-byte extension, (version 5) two uint32 lengths + the network strings, W / m / v, the walker
+    records [n][448 B], rng_t, dxoff, mat, ep_acc (f64), ep_len (i32), int32 n_props, the wk_prop
+    records and [n][pstride] floats -- the length, the header and every section the wrapper can
+    read back, bit for bit"""
+    import struct
+    n, T = 5, 2
+    dx = np.array([0.0, 12.5, 25.0, 50.0, 187.5], np.float32)
+    mat = np.array([0, 1, 2, 3, 4], np.int32)
+    if general:
+        e = wk.Engine(n, seed=SEED, Horizon=T, LanesPerWalker=1, NetworkKernels=1,
+                      CriticNeuralNetwork=CKPT_NETS[0], ActorNeuralNetwork=CKPT_NETS[1])
+        n_props, pstride = 0, 0
+    else:
+        e = wk.Engine(n, seed=SEED, Horizon=T, LanesPerWalker=1)
+        e.set_scene([wk.make_prop("Square", cx=300.0, cy=700.0)])
+        n_props, pstride = 1, 2 * 4 + 6  # a square's x, y rows + centroid, velocity, w, angle
+    e.set_offsets(dx)
+    e.set_materials(mat)
+    e.rollout()
+    dones = e.get_trajectory(T)["dones"]
+    e.ppo_update(minibatch=5)
+    ck = tmp_path / "layout.ckpt"
+    e.checkpoint_save(ck)
+    raw = ck.read_bytes()
+    w, (m, v, adam_t), st = e.get_weights(), e.get_adam(), e.get_state()
+    npar = e.nparam
+    assert (npar == wk.NPARAM) != general and adam_t == e.cfg.Epochs * (n * T // 5) > 0
+
+    hdr = struct.unpack_from("<6IQ3iI", raw, 0)
+    assert struct.calcsize("<6IQ3iI") == 48
+    assert hdr == (0x4B434B57, 5 if general else 4, n, wk.STATE_FLOATS, npar, adam_t, SEED,
+                   e.cfg.EnvOffset, e.cfg.Iterations, e.cfg.MaxTimesteps, T)
+    assert struct.unpack_from("<4i", raw, 48) == (0, 1, int(general), 0)  # RoughFloor, lanes, net
+    at = 64
+    if general:
+        lc, la = struct.unpack_from("<2I", raw, at)
+        assert (lc, la) == (len(CKPT_NETS[0]), len(CKPT_NETS[1]))
+        assert raw[at + 8:at + 8 + lc + la] == (CKPT_NETS[0] + CKPT_NETS[1]).encode()
+        at += 8 + lc + la
+
+    def section(dtype, count):
+        nonlocal at
+        a = np.frombuffer(raw, dtype, count, at)
+        at += a.nbytes
+        return a
+
+    for name, ref in (("W", w), ("m", m), ("v", v)):
+        np.testing.assert_array_equal(section(np.uint32, npar), ref.view(np.uint32), err_msg=name)
+    assert wk.STATE_FLOATS * 4 == 448
+    np.testing.assert_array_equal(section(np.uint32, n * wk.STATE_FLOATS),
+                                  st.reshape(-1).view(np.uint32))
+    rng_t = section(np.uint32, n)
+    alive = ~dones.astype(bool).any(axis=0)
+    assert alive.any() and (rng_t[alive] == T).all()
+    np.testing.assert_array_equal(section(np.uint32, n), dx.view(np.uint32))
+    np.testing.assert_array_equal(section(np.int32, n), mat)
+    section(np.float64, n)  # ep_acc, ep_len: position and length only
+    section(np.int32, n)
+    assert section(np.int32, 1)[0] == n_props
+    at += 48 * n_props + 4 * n * pstride  # wk_prop records, prop state
+    assert at == len(raw)
+    assert len(raw) == (48 + 16 + (8 + len("".join(CKPT_NETS)) if general else 0) + 3 * 4 * npar
+                        + n * 448 + 3 * 4 * n + 8 * n + 4 * n + 4 + 48 * n_props + 4 * n * pstride)
+    if n_props:  # the description record, as given
+        assert raw[len(raw) - 4 * n * pstride - 48:len(raw) - 4 * n * pstride] == bytes(
+            wk.make_prop("Square", cx=300.0, cy=700.0))
+    e.close()
+
+
 def test_contexts_on_two_devices(wk):
     """every entry point binds the context's device, so two contexts on devices
     0 and 1 used alternately from one thread keep their buffers and kernels apart, and the
