@@ -128,6 +128,17 @@ typedef struct wk_config {
                                values, wk_get / wk_set_bootstrap_values); a terminal step still
                                resets the scan to 0, an episode ended by MaxTimesteps included.
                                Anything else is WK_ERR_CONFIG.  Not part of the JSON document */
+  float TargetKL;           /* 0 (default): off -- wk_ppo_update launches what it always did and stays
+                               asynchronous.  > 0: after every epoch of wk_ppo_update, the last
+                               included, the pass of wk_policy_stats runs over the whole trajectory
+                               buffer and its record is copied to the host (one stream
+                               synchronise per epoch); when its kl > TargetKL (strict; a NaN never
+                               stops) the remaining epochs are not run.  wk_update_stats_get
+                               returns the last check.  Negative or non-finite is WK_ERR_CONFIG
+                               before a device is touched.  One GPU: ranks deciding on their own
+                               shards would desert each other mid-exchange, so wk_comm_init,
+                               wk_comm_init_host, wk_comm_ipc_handle and wk_comm_init_ipc return
+                               WK_ERR_CONFIG on such a context.  Not part of the JSON document */
 } wk_config;
 
 /* The host-only fields of the reference's JSON configuration (SerializableHyperparameters,
@@ -226,6 +237,30 @@ typedef struct wk_rollout_stats {
   uint32_t fault_or;     /* OR of per-env fault bits */
   int32_t pad;
 } wk_rollout_stats;
+
+/* What the current actor and critic make of the trajectory buffer (wk_policy_stats), and the
+ * last per-epoch check of a TargetKL > 0 update (wk_update_stats_get).  Per (row, action
+ * dimension) entry, exactly as the gradient kernels define them: mean = tanhf(z3), lp = lp_const -
+ * ((act - mean) / std)^2 / 2 and ratio = expf(lp - logp_old) in fp32, the clip bounds 1 +- Epsilon
+ * in fp32.  A row is skipped, and leaves every statistic untouched, exactly when
+ * expf(logp_old) == 0 in any of its four dimensions (the gradient kernels' skip rule).  d = lp -
+ * logp_old is the fp32 difference; the sums continue in double.  With no counted row every mean
+ * and ratio_max are NaN; non-finite inputs of counted rows propagate. */
+typedef struct wk_ppo_stats {
+  int64_t samples;            /* trajectory rows counted */
+  int64_t skipped;            /* rows the skip rule drops */
+  double kl;                  /* mean over counted entries of expm1(d) - d (>= 0) */
+  double kl_k1;               /* mean of -d */
+  double clip_fraction;       /* share of entries with ratio > 1 + Epsilon or < 1 - Epsilon */
+  double ratio_max;           /* largest ratio among counted entries */
+  double surrogate;           /* mean of min(ratio * adv, clip(ratio) * adv), the fp32 products */
+  double value_loss;          /* mean over counted rows of (V_new - ret)^2 */
+  double explained_variance;  /* 1 - Var(ret - V_new) / Var(ret), population variances over the
+                                 counted rows; NaN when Var(ret) is 0 (not above the rounding of
+                                 its own sums) */
+  int32_t epochs_run;         /* wk_update_stats_get only; 0 from wk_policy_stats */
+  int32_t stopped_early;      /* wk_update_stats_get only: 1 when fewer epochs ran than asked */
+} wk_ppo_stats;
 
 /* one finished episode (data collection) */
 typedef struct wk_episode_rec {
@@ -412,6 +447,21 @@ int wk_compute_returns(wk_ctx* ctx);
 int wk_get_bootstrap_values(wk_ctx* ctx, float* v /* n_env */);
 int wk_set_bootstrap_values(wk_ctx* ctx, const float* v /* n_env */);
 int wk_ppo_update(wk_ctx* ctx, const wk_ppo_args* args, float* critic_diag, float* actor_diag);
+/* The context's current actor and critic on every row of the valid trajectory buffer (T_valid x
+ * n_env, layout [t][e]): one forward-only matrix-core pass and an ordered reduction (no atomics:
+ * the same inputs give the same bytes).  It uses the buffer's returns and advantages (after the
+ * normalisation when NormalizeAdvantages is set) and computes them first when they are stale,
+ * with wk_ppo_update's rules: WK_ERR_STATE without a trajectory, or on a ReturnsMode = 1 context
+ * without bootstrap values.  The optional outputs receive the per-row fp32 log-densities
+ * logp_new[t][e][4] and values values_new[t][e] of every row, skipped rows included.  No state a
+ * later call can observe changes: weights, Adam, Philox counters, trajectory, whether the returns
+ * count as valid, logs.  With a communicator it reports this rank's shard.
+ * wk_update_stats_get: the record of the last per-epoch check of this context's last
+ * wk_ppo_update, with epochs_run and stopped_early; WK_ERR_STATE when that update made no check
+ * (TargetKL = 0, or no update yet). */
+int wk_policy_stats(wk_ctx* ctx, wk_ppo_stats* out, float* logp_new /* T*n*4 or NULL */,
+                    float* values_new /* T*n or NULL */);
+int wk_update_stats_get(wk_ctx* ctx, wk_ppo_stats* out);
 /* Train(Batch) on caller data: B samples, divisor b_div; grads_out (optional, WK_NPARAM)
  * receives the accumulated gradient before Adam. Returns skipped-sample count in *skipped. */
 int wk_train_batch(wk_ctx* ctx, int B, float b_div, const float* states, const float* actions,

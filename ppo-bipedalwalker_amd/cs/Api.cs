@@ -109,6 +109,19 @@ namespace NEA.Walker
     using NEA.Native;
     using NEA.Objects;
 
+    // What an update did to the policy (no counterpart in the reference, which reports two loss
+    // numbers): the current networks on the context's trajectory buffer -- approximate KL to the
+    // collecting policy, clip fraction, explained variance -- and the last per-epoch check of a
+    // TargetKL > 0 update.  null on failure, logged like every other call
+    public static class PolicyStatistics
+    {
+        public static WkPpoStats? Current(IntPtr ctx, float[]? logpNew = null, float[]? valuesNew = null, Action<string>? log = null) =>
+            Wk.Ok(ctx, Wk.wk_policy_stats(ctx, out var s, logpNew, valuesNew), "Exception while reading the policy statistics", log) ? s : null;
+
+        public static WkPpoStats? LastUpdate(IntPtr ctx, Action<string>? log = null) =>
+            Wk.Ok(ctx, Wk.wk_update_stats_get(ctx, out var s), "Exception while reading the update's statistics", log) ? s : null;
+    }
+
     // Walker/Walker.cs:49-223 for walker `Index` of a context (a Walker owns no state of its own:
     // its bodies, torques, Collided flags and episode counter live in the context's records)
     public sealed class Walker

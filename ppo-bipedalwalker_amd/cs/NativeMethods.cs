@@ -41,6 +41,9 @@ public struct WkConfig
     // ReturnsMode: 0 = the reference's returns (GAE never chained, 0 at every horizon cut), 1 = chained GAE(Lambda) and the
     // critic's value at the cut (wk_get / wk_set_bootstrap_values) -- a host that trains on complete episodes passes zeros
     public int LanesPerWalker, NetworkKernels, ReturnsMode;
+    // TargetKL: 0 = off, above 0 = after every epoch of wk_ppo_update the pass of wk_policy_stats runs over the trajectory buffer
+    // and the remaining epochs are not run once its Kl exceeds the target (wk_update_stats_get returns the last check)
+    public float TargetKL;
 }
 
 // SerializableHyperparameters' host-only fields (Hyperparameters.cs:11-77)
@@ -118,6 +121,15 @@ public struct WkRolloutStats
     public long Episodes, EnvSteps;
     public uint FaultOr;
     public int Pad;
+}
+
+// wk_policy_stats / wk_update_stats_get: the current actor and critic on the trajectory buffer
+[StructLayout(LayoutKind.Sequential)]
+public struct WkPpoStats
+{
+    public long Samples, Skipped;
+    public double Kl, KlK1, ClipFraction, RatioMax, Surrogate, ValueLoss, ExplainedVariance;
+    public int EpochsRun, StoppedEarly;
 }
 
 [StructLayout(LayoutKind.Sequential)]
@@ -207,6 +219,8 @@ public static class Wk
     [DllImport(Lib)] public static extern int wk_get_bootstrap_values(IntPtr ctx, float[] v);
     [DllImport(Lib)] public static extern int wk_set_bootstrap_values(IntPtr ctx, float[] v);
     [DllImport(Lib)] public static extern int wk_ppo_update(IntPtr ctx, ref WkPpoArgs args, out float criticDiag, out float actorDiag);
+    [DllImport(Lib)] public static extern int wk_policy_stats(IntPtr ctx, out WkPpoStats stats, float[]? logpNew, float[]? valuesNew);
+    [DllImport(Lib)] public static extern int wk_update_stats_get(IntPtr ctx, out WkPpoStats stats);
     [DllImport(Lib)] public static extern int wk_train_batch(IntPtr ctx, int B, float bDiv, float[] states, float[] actions, float[] logpOld, float[] returns, float[] adv, out float criticDiag, out float actorDiag, float[]? gradsOut, int applyAdam, out int skipped);
     [DllImport(Lib)] public static extern int wk_minibatch_gradient(IntPtr ctx, int B, float bDiv, float[] states, float[] actions, float[] logpOld, float[] returns, float[] adv, out float criticDiag, out float actorDiag, float[]? gradsOut, out int skipped);
 

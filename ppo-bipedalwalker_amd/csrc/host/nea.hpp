@@ -117,7 +117,9 @@ namespace PPO {
 // network string on the general kernels (the reference's network menu, ConsoleRenderer.cs:188-189).
 // c.ReturnsMode = 1 selects chained GAE(Lambda) and the critic's value at a horizon cut
 // (wk_get / wk_set_bootstrap_values); 0, the default, is the reference's arithmetic, and this
-// host, which trains on what wk_rollout recorded, needs no further call in either mode
+// host, which trains on what wk_rollout recorded, needs no further call in either mode.
+// c.TargetKL > 0 ends an update's epochs once the approximate KL to the collecting policy passes
+// it (PPOAgent::UpdateStatistics returns the last check)
 struct Hyperparameters {
   wk_config c;
   Hyperparameters() { wk_config_defaults(&c); }
@@ -177,6 +179,21 @@ class PPOAgent {
     if (wk_ppo_update(ctx_, &a, &cd, &ad) != WK_OK)
       LogError(std::string("Exception while training: ") + wk_last_error(ctx_));
     return {cd, ad};
+  }
+  // What the current networks make of the device trajectory (no counterpart in the reference):
+  // approximate KL to the collecting policy, clip fraction, explained variance, ...; and the last
+  // per-epoch check of a TargetKL > 0 Train.  A zeroed record on failure
+  wk_ppo_stats PolicyStatistics(std::vector<float>* logpNew = nullptr, std::vector<float>* valuesNew = nullptr) {
+    wk_ppo_stats s{};
+    if (wk_policy_stats(ctx_, &s, logpNew ? logpNew->data() : nullptr, valuesNew ? valuesNew->data() : nullptr) != WK_OK)
+      LogError(std::string("Exception while reading the policy statistics: ") + wk_last_error(ctx_));
+    return s;
+  }
+  wk_ppo_stats UpdateStatistics() {
+    wk_ppo_stats s{};
+    if (wk_update_stats_get(ctx_, &s) != WK_OK)
+      LogError(std::string("Exception while reading the update's statistics: ") + wk_last_error(ctx_));
+    return s;
   }
   std::vector<float> Save() {  // NeuralNetwork.Save order (flat)
     std::vector<float> p(NumParams());

@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -70,6 +71,9 @@ struct wk_ctx {
   // ReturnsMode = 1: the value each walker's reverse scan starts from (part of the trajectory)
   float* vlast = nullptr;     // [n]
   bool vlast_valid = false;
+  // TargetKL > 0: the last per-epoch check of the last wk_ppo_update (wk_update_stats_get)
+  wk_ppo_stats upd_stats{};
+  bool upd_stats_valid = false;
   // data collection (ConsoleRenderer.AddTotalEpisodeReward / AddCriticLoss / AddActorLoss)
   int collect = 1;
   uint32_t rollout_steps = 0;  // env-steps taken by wk_rollout so far (episode log clock)
@@ -285,6 +289,7 @@ void wk_config_defaults(wk_config* c) {
   c->RandomizeMaterial = 0;
   c->NetworkKernels = 0;
   c->ReturnsMode = 0;
+  c->TargetKL = 0.0f;
 }
 
 const char* wk_version(void) { return "wk 0.1 (gfx950)"; }
@@ -330,6 +335,8 @@ static int validate(const wk_config* c, std::string& why) {
   }
   if (c->ReturnsMode != 0 && c->ReturnsMode != 1)
     return bad("ReturnsMode must be 0 (the reference's returns) or 1 (chained GAE, bootstrap at the cut)");
+  if (!std::isfinite(c->TargetKL) || c->TargetKL < 0.0f)
+    return bad("TargetKL must be finite and >= 0 (0: no early stop)");
   if (c->Horizon <= 0) return bad("Horizon must be > 0");
   if (c->Minibatch < 0) return bad("Minibatch must be >= 0");
   if (c->LanesPerWalker != 0 && c->LanesPerWalker != 1 && c->LanesPerWalker != 2 &&
@@ -1573,6 +1580,91 @@ static wk::GradArgs traj_grad_args(wk_ctx* c, int M, float b_div) {
   return g;
 }
 
+// the kernel family's statistics pass (the seam's third part, see launch_policy_for)
+static int stats_blocks_for(wk_ctx* c, int rows) {
+  return c->general ? wk::net_stats_blocks(rows) : wk::ppo_stats_blocks(rows);
+}
+static hipError_t launch_stats_for(wk_ctx* c, const wk::StatsArgs& a, int nblocks) {
+  return c->general ? wk::launch_net_stats(a, c->net_dev, c->act_rows, c->stream)
+                    : wk::launch_ppo_stats(a, nblocks, c->stream);
+}
+
+// wk_ppo_stats from the device's record: the host divides
+static void stats_from_rec(const wk::StatsRec& r, wk_ppo_stats* o) {
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  memset(o, 0, sizeof(*o));
+  o->samples = r.rows;
+  o->skipped = r.skipped;
+  const double n = (double)r.rows, ne = 4.0 * n;  // (0 / 0: every mean of no rows is NaN)
+  o->kl = r.kl / ne;
+  o->kl_k1 = r.k1 / ne;
+  o->clip_fraction = (double)r.clipped / ne;
+  o->ratio_max = r.rows > 0 ? r.rmax : nan;
+  o->surrogate = r.surr / ne;
+  o->value_loss = r.see / n;
+  // population variances from the sums; a Var(ret) within the rounding of its own sums (n terms
+  // of srr, each to 2^-53) is the variance of a constant: 0
+  const double mr = r.sr / n, me = r.se / n;
+  const double var_r = r.srr / n - mr * mr, var_e = r.see / n - me * me;
+  const bool flat = var_r <= 4.0 * n * 0x1p-53 * (r.srr / n);
+  o->explained_variance = (r.rows > 0 && !flat) ? 1.0 - var_e / var_r : nan;
+  if (var_r != var_r) o->explained_variance = nan;
+}
+
+// The statistics pass over the valid trajectory buffer with the current weights (wk_policy_stats
+// and the per-epoch check of a TargetKL > 0 update): forward kernel, k_stats_finish, the record
+// and the optional per-row outputs copied to the host.  Stale returns are computed first, and
+// whether they count as valid is left as it was.
+static int stats_impl(wk_ctx* c, wk_ppo_stats* out, float* logp_new, float* values_new) {
+  if (c->T_valid <= 0) { SETERR(c, "wk_policy_stats before wk_rollout / wk_set_trajectory"); return WK_ERR_STATE; }
+  if (!c->returns_valid) {
+    int r = returns_impl(c);
+    if (r) return r;
+    c->returns_valid = false;
+  }
+  const size_t rows = (size_t)c->n * c->T_valid;
+  if (rows > (size_t)INT32_MAX / 16) { SETERR(c, "wk_policy_stats: %zu rows exceed the kernel's index range", rows); return WK_ERR_ARG; }
+  const int nblocks = stats_blocks_for(c, (int)rows);
+  wk::StatsArgs a{};
+  a.g = grad_base(c);
+  a.g.states = c->ts; a.g.actions = c->ta; a.g.logp_old = c->tlp; a.g.returns = c->tret; a.g.adv = c->tadv;
+  a.g.pool = (uint32_t)rows;
+  a.g.samples = (int)rows;
+  wk::StatsRec* d_rec;
+  if (carve(c, &c->scratch2, &c->scratch2_bytes,
+            {{&a.partial, sizeof(wk::StatsRec) * (size_t)nblocks}, {&d_rec, sizeof(wk::StatsRec)},
+             {&a.logp_new, logp_new ? sizeof(float) * 4 * rows : 0},
+             {&a.values_new, values_new ? sizeof(float) * rows : 0}}))
+    return WK_ERR_HIP;
+  HIPCHK(c, launch_stats_for(c, a, nblocks));
+  HIPCHK(c, wk::launch_stats_finish(a.partial, nblocks, d_rec, c->stream));
+  wk::StatsRec rec;
+  HIPCHK(c, hipMemcpyAsync(&rec, d_rec, sizeof(rec), hipMemcpyDeviceToHost, c->stream));
+  if (logp_new)
+    HIPCHK(c, hipMemcpyAsync(logp_new, a.logp_new, sizeof(float) * 4 * rows, hipMemcpyDeviceToHost, c->stream));
+  if (values_new)
+    HIPCHK(c, hipMemcpyAsync(values_new, a.values_new, sizeof(float) * rows, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  stats_from_rec(rec, out);
+  return WK_OK;
+}
+
+int wk_policy_stats(wk_ctx* c, wk_ppo_stats* out, float* logp_new, float* values_new) {
+  DevGuard dg_(c);
+  if (!c || !out) return WK_ERR_ARG;
+  return stats_impl(c, out, logp_new, values_new);
+}
+
+int wk_update_stats_get(wk_ctx* c, wk_ppo_stats* out) {
+  if (!c || !out) return WK_ERR_ARG;
+  if (!c->upd_stats_valid) {
+    SETERR(c, "wk_update_stats_get: the last wk_ppo_update made no check (TargetKL = 0, or no update yet)");
+    return WK_ERR_STATE;
+  }
+  *out = c->upd_stats;
+  return WK_OK;
+}
+
 static int ppo_update_impl(wk_ctx* c, const wk_ppo_args* args);
 // The gradient kernel alone, `reps` back-to-back launches on minibatch 0 of the keyed sequence
 // (update 0, epoch 0) of the current trajectory, between one HIP-event pair on the context's
@@ -1689,6 +1781,7 @@ int wk_ppo_update(wk_ctx* c, const wk_ppo_args* args, float* critic_diag, float*
 }
 
 static int ppo_update_impl(wk_ctx* c, const wk_ppo_args* args) {
+  c->upd_stats_valid = false;
   if (!c->returns_valid) {
     int r = returns_impl(c);
     if (r) return r;
@@ -1710,6 +1803,16 @@ static int ppo_update_impl(wk_ctx* c, const wk_ppo_args* args) {
       g.base = (uint32_t)j * (uint32_t)M;
       int r = minibatch(c, g, wpb, 1);
       if (r) return r;
+    }
+    // TargetKL: the policy's distance from the one that collected the data, after every epoch
+    // (the last included); past the target the remaining epochs are not run (a NaN never stops)
+    if (c->cfg.TargetKL > 0.0f) {
+      if (int r = stats_impl(c, &c->upd_stats, nullptr, nullptr)) return r;
+      const bool stop = c->upd_stats.kl > (double)c->cfg.TargetKL;
+      c->upd_stats.epochs_run = e + 1;
+      c->upd_stats.stopped_early = (stop && e + 1 < epochs) ? 1 : 0;
+      c->upd_stats_valid = true;
+      if (stop) break;
     }
   }
   return WK_OK;
@@ -1767,7 +1870,13 @@ int wk_minibatch_gradient(wk_ctx* c, int B, float b_div, const float* s, const f
   return batch_impl(c, 0, B, b_div, s, a, lpo, ret, adv, cd, ad, grads_out, 0, skipped);
 }
 
-static int refuse_general_comm(wk_ctx* c) {
+static int refuse_comm(wk_ctx* c) {
+  // ranks that stop on their own shards' KL would desert each other mid-exchange
+  if (c->cfg.TargetKL > 0.0f) {
+    SETERR(c, "the multi-GPU gradient exchange refuses a TargetKL > 0 context: every rank would "
+              "decide on its own shard's statistics");
+    return WK_ERR_CONFIG;
+  }
   if (!c->general) return WK_OK;
   SETERR(c, "the multi-GPU gradient exchange serves the built-in kernels only (NetworkKernels = 0)");
   return WK_ERR_CONFIG;
@@ -1786,7 +1895,7 @@ int wk_comm_unique_id(uint8_t* id) {
 int wk_comm_init(wk_ctx* c, int rank, int nranks, const uint8_t* id) {
   DevGuard dg_(c);
   if (!c || !id || nranks <= 0 || rank < 0 || rank >= nranks) return WK_ERR_ARG;
-  if (int r = refuse_general_comm(c)) return r;
+  if (int r = refuse_comm(c)) return r;
   if (c->host_ar) { SETERR(c, "the context already has a host all-reduce"); return WK_ERR_STATE; }
   HIPCHK(c, hipSetDevice(c->device));
   ncclUniqueId u;
@@ -1801,7 +1910,7 @@ int wk_comm_init(wk_ctx* c, int rank, int nranks, const uint8_t* id) {
 int wk_comm_init_host(wk_ctx* c, int rank, int nranks, wk_host_allreduce_fn fn, void* user) {
   DevGuard dg_(c);
   if (!c || !fn || nranks <= 0 || rank < 0 || rank >= nranks) return WK_ERR_ARG;
-  if (int r = refuse_general_comm(c)) return r;
+  if (int r = refuse_comm(c)) return r;
   if (c->comm) { SETERR(c, "the context already has an RCCL communicator"); return WK_ERR_STATE; }
   c->host_ar = fn;
   c->host_ar_user = user;
@@ -1818,7 +1927,7 @@ static_assert(sizeof(hipIpcMemHandle_t) == kIpcDevOff && WK_IPC_HANDLE_BYTES == 
 int wk_comm_ipc_handle(wk_ctx* c, uint8_t* handle) {
   DevGuard dg_(c);
   if (!c || !handle) return WK_ERR_ARG;
-  if (int r = refuse_general_comm(c)) return r;
+  if (int r = refuse_comm(c)) return r;
   if (!c->xch) {
     // uncached (MTYPE UC) device memory: the peers read it over xGMI and this GPU writes it
     // through no cache; coarse-grained hipMalloc memory is the fallback where the driver cannot
@@ -1851,7 +1960,7 @@ int wk_comm_ipc_handle(wk_ctx* c, uint8_t* handle) {
 int wk_comm_init_ipc(wk_ctx* c, int rank, int nranks, const uint8_t* handles) {
   DevGuard dg_(c);
   if (!c || !handles || nranks <= 0 || rank < 0 || rank >= nranks) return WK_ERR_ARG;
-  if (int r = refuse_general_comm(c)) return r;
+  if (int r = refuse_comm(c)) return r;
   if (nranks > wk::XCH_MAX_RANKS) { SETERR(c, "the IPC exchange spans at most %d ranks", (int)wk::XCH_MAX_RANKS); return WK_ERR_ARG; }
   if (c->comm || c->host_ar || c->ipc) { SETERR(c, "the context already has an all-reduce"); return WK_ERR_STATE; }
   if (!c->xch) { SETERR(c, "wk_comm_ipc_handle first"); return WK_ERR_STATE; }

@@ -210,6 +210,35 @@ hipError_t launch_net_reduce(const float* partial, int nblocks, int np, float* g
                              hipStream_t s);
 hipError_t launch_net_xavier(float* W, uint64_t seed, const NetDesc* nets, int np, hipStream_t s);
 
+// Policy statistics over the trajectory (wk_policy_stats; k_ppo_stats in wk_stats.hip for the
+// built-in networks, k_net_stats in wk_net.hip for the general ones, wk_stats.h the arithmetic
+// they share).  StatsRec is the record every stage carries -- counts as integers, sums in double,
+// the largest ratio -- as STATS_FIELDS 64-bit words: one per block from the forward kernel, one
+// from k_stats_finish (the blocks' records in block order), which the host divides.
+struct StatsRec {
+  long long rows, skipped, clipped;  // counted rows, skipped rows, clipped (row, dim) entries
+  double kl, k1, surr;               // over counted entries: expm1(d) - d, -d, min(r adv, clip(r) adv)
+  double sr, srr, se, see;           // over counted rows: ret, ret^2, e = ret - V, e^2
+  double rmax;                       // largest ratio (-inf: none; a NaN stays)
+};
+enum : int { STATS_FIELDS = 11, STATS_COUNTS = 3, STATS_RMAX = 10 };
+static_assert(sizeof(StatsRec) == 8 * STATS_FIELDS, "StatsRec is STATS_FIELDS 64-bit words");
+// the built-in kernel's grid: at most STATS_MAX_BLOCKS blocks of STATS_WAVES waves, every wave
+// striding over the 16-row chunks (one grid pass = STATS_MAX_BLOCKS * STATS_WAVES * 16 rows)
+enum : int { STATS_MAX_BLOCKS = 512, STATS_WAVES = 4 };
+struct StatsArgs {
+  GradArgs g;               // the rows in buffer order: samples = rows, base 0, no permutation
+  float* logp_new;          // [rows][4] or null
+  float* values_new;        // [rows] or null
+  unsigned long long* partial;  // [blocks][STATS_FIELDS]
+};
+int ppo_stats_blocks(int rows);
+hipError_t launch_ppo_stats(const StatsArgs& a, int nblocks, hipStream_t s);
+int net_stats_blocks(int rows);
+hipError_t launch_net_stats(const StatsArgs& a, const NetDesc* nets, int act_rows, hipStream_t s);
+hipError_t launch_stats_finish(const unsigned long long* partial, int nblocks, StatsRec* out,
+                               hipStream_t s);
+
 // data collection: per-episode totals of a recorded rollout appended to the device log;
 // layout == wk_episode_rec (include/wk_api.h)
 struct EpisodeRecDev {

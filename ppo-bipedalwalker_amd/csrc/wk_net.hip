@@ -25,6 +25,7 @@
 #include "wk_kernels.h"
 #include "wk_net.h"
 #include "wk_sample.h"
+#include "wk_stats.h"
 #include "wk_tail.h"
 
 namespace wk {
@@ -251,6 +252,54 @@ __global__ __launch_bounds__(64) void k_net_policy(EnvParams P, const NetDesc* _
   }
 }
 
+// Policy statistics over the trajectory (wk_policy_stats) for the general networks: k_net_policy's
+// tile set-up, net_forward on the actor and then on the critic over the same LDS image, and the
+// per-entry arithmetic and double records of wk_stats.h (lane (s, d): dimension d of row s).
+// Block b owns the consecutive tiles [b tpb, (b + 1) tpb), as in k_net_grad, and writes one
+// record; k_stats_finish (wk_stats.hip) sums the records in block order.  Every row is evaluated,
+// the skipped ones too (their log-densities and values are outputs); a row's column of the
+// activation image never meets another row's.
+__global__ __launch_bounds__(64) void k_net_stats(StatsArgs sa, const NetDesc* __restrict__ nets,
+                                                  int act_rows, int tiles_per_block) {
+  using namespace nt;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const GradArgs& ga = sa.g;
+  float* act = lds;
+  const int lane = threadIdx.x, s = lane & 15, d = lane >> 4;
+  const NetDesc* critic = nets;
+  const NetDesc* actor = nets + 1;
+  const int ntiles = (ga.samples + NS - 1) / NS;
+  const int t0 = blockIdx.x * tiles_per_block;
+  const int t1 = min(t0 + tiles_per_block, ntiles);
+  StatsAcc acc;
+#pragma unroll 1
+  for (int tile = t0; tile < t1; tile++) {
+    const int pos = tile * NS + s;
+    const bool live = pos < ga.samples;
+    const size_t idx = live ? (size_t)pos : 0;
+    const float lpo = ga.logp_old[idx * 4 + d], ac = ga.actions[idx * 4 + d];
+    const float ret = ga.returns[idx], adv = ga.adv[idx];
+#pragma unroll
+    for (int j = 0; j < 3; j++) act[(3 * d + j) * LS + s] = live ? ga.states[idx * 12 + 3 * d + j] : 0.0f;
+    __syncthreads();
+    net_forward(actor, ga.W, act, lane);
+    const float mean = act[(actor->row_end + d) * LS + s];
+    __syncthreads();  // the means are read before the critic's layers overwrite the image
+    net_forward(critic, ga.W, act, lane);
+    const float V = act[critic->row_end * LS + s];
+    const float lp = stats_entry(acc, ga, live, d == 0, mean, V, ac, lpo, ret, adv);
+    if (live) {
+      if (sa.logp_new) sa.logp_new[(size_t)pos * 4 + d] = lp;
+      if (sa.values_new && d == 0) sa.values_new[pos] = V;
+    }
+    __syncthreads();  // the next tile rewrites the image
+  }
+  unsigned long long* rec = (unsigned long long*)(lds + ((act_rows * LS + 1) & ~1));
+  stats_put(acc, rec, lane);
+  __syncthreads();
+  stats_block_fold<1>(rec, lane, sa.partial + (size_t)blockIdx.x * STATS_FIELDS);
+}
+
 struct NetGradArgs {
   GradArgs g;
   const NetDesc* nets;   // [0] critic, [1] actor
@@ -419,6 +468,9 @@ __global__ void k_net_xavier(float* W, uint64_t seed, const NetDesc* __restrict_
 
 // ---- host side ----
 static size_t policy_lds(int act_rows) { return sizeof(float) * (size_t)act_rows * nt::LS; }
+static size_t stats_lds(int act_rows) {
+  return sizeof(float) * (size_t)((act_rows * nt::LS + 1) & ~1) + sizeof(unsigned long long) * STATS_FIELDS * 64;
+}
 static size_t grad_lds(int act_rows) {
   return sizeof(float) * ((size_t)(act_rows + 2 * nt::GROWS) * nt::LS + nt::M_END);
 }
@@ -430,6 +482,9 @@ hipError_t configure_net_kernels() {
   if (e == hipSuccess)
     e = hipFuncSetAttribute((const void*)k_net_policy, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)policy_lds(rows));
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute((const void*)k_net_stats, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)stats_lds(rows));
   return e;
 }
 
@@ -469,6 +524,15 @@ hipError_t launch_net_grad(const GradArgs& g, const NetDesc* nets, int act_rows,
   A.tiles_per_block = net_tiles_per_block(g.samples);
   A.act_rows = act_rows;
   hipLaunchKernelGGL(k_net_grad, dim3(net_grad_blocks(g.samples)), dim3(64), grad_lds(act_rows), s, A);
+  return hipGetLastError();
+}
+
+// the statistics pass: k_net_grad's assignment of tiles to blocks
+int net_stats_blocks(int rows) { return net_grad_blocks(rows); }
+
+hipError_t launch_net_stats(const StatsArgs& a, const NetDesc* nets, int act_rows, hipStream_t s) {
+  hipLaunchKernelGGL(k_net_stats, dim3(net_stats_blocks(a.g.samples)), dim3(64), stats_lds(act_rows), s, a,
+                     nets, act_rows, net_tiles_per_block(a.g.samples));
   return hipGetLastError();
 }
 

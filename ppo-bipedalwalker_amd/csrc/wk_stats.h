@@ -1,0 +1,102 @@
+// wk_stats.h -- the arithmetic k_ppo_stats (wk_stats.hip) and k_net_stats (wk_net.hip) share:
+// the per-entry statistics of one (row, action dimension), a lane's running sums, and the
+// ordered folds lane -> wave -> block.  Device code only.
+#pragma once
+#include "wk_kernels.h"
+#include "wk_mfma_layout.h"
+
+namespace wk {
+
+// a lane's sums across its chunks, in chunk order: doubles, the counts as integers
+struct StatsAcc {
+  int rows = 0, skipped = 0, clipped = 0;
+  double kl = 0.0, k1 = 0.0, surr = 0.0, sr = 0.0, srr = 0.0, se = 0.0, see = 0.0;
+  float rmax = -__builtin_inff();
+};
+
+// the larger of the two; a NaN on either side stays
+__device__ __forceinline__ double stats_max(double m, double v) { return (v > m || v != v) ? v : m; }
+
+// One entry, in lane (row n, dim g) of a wave whose 64 lanes are all active: the quantities as
+// the gradient kernels define them (wk_ppo_mfma.hip "PPO derivative", PPOAgent.cs:234-326) --
+// fr, lp, rr and the clip in fp32 -- then d = lp - lpo in fp32 and everything after it in double.
+// valid: the row exists; the skip rule (expf(lpo) == 0 in any of the row's four dimensions)
+// decides with it whether the row counts.  Returns lp (for every row).
+__device__ __forceinline__ float stats_entry(StatsAcc& a, const GradArgs& ga, bool valid, bool row_lane,
+                                             float mean, float V, float act, float lpo, float ret,
+                                             float adv) {
+  float fr = (act - mean) / ga.std_;
+  fr *= fr;
+  fr /= 2.0f;
+  const float lp = ga.lp_const - fr;
+  const float d = lp - lpo;
+  const float rr = expf(d);
+  const float cr = rr >= ga.upper ? ga.upper : (rr <= ga.lower ? ga.lower : rr);
+  const float cra = cr * adv, ra = rr * adv;
+  const float sg = ra <= cra ? ra : cra;
+  const float eo = expf(lpo);
+  float zd = eo == 0.0f ? 1.0f : 0.0f;
+  zd = rows_max4(zd);
+  const bool use = valid && zd == 0.0f;
+  if (use) {
+    const double dd = (double)d;
+    a.kl += expm1(dd) - dd;
+    a.k1 += -dd;
+    a.surr += (double)sg;
+    a.clipped += (rr > ga.upper || rr < ga.lower) ? 1 : 0;
+    a.rmax = (rr > a.rmax || rr != rr) ? rr : a.rmax;
+    if (row_lane) {
+      const double r = (double)ret, e = r - (double)V;
+      a.rows += 1;
+      a.sr += r;
+      a.srr += r * r;
+      a.se += e;
+      a.see += e * e;
+    }
+  } else if (valid && row_lane) {
+    a.skipped += 1;
+  }
+  return lp;
+}
+
+// a lane's record into its wave's LDS image [STATS_FIELDS][64] (64-bit words)
+__device__ __forceinline__ void stats_put(const StatsAcc& a, unsigned long long* rec, int lane) {
+  rec[0 * 64 + lane] = (unsigned long long)(long long)a.rows;
+  rec[1 * 64 + lane] = (unsigned long long)(long long)a.skipped;
+  rec[2 * 64 + lane] = (unsigned long long)(long long)a.clipped;
+  const double v[7] = {a.kl, a.k1, a.surr, a.sr, a.srr, a.se, a.see};
+#pragma unroll
+  for (int i = 0; i < 7; i++) rec[(STATS_COUNTS + i) * 64 + lane] = (unsigned long long)__double_as_longlong(v[i]);
+  rec[STATS_RMAX * 64 + lane] = (unsigned long long)__double_as_longlong((double)a.rmax);
+}
+
+// two words of field f combined: the counts as integers, the sums as doubles, the maximum
+__device__ __forceinline__ unsigned long long stats_zero(int f) {
+  return f == STATS_RMAX ? (unsigned long long)__double_as_longlong(-(double)__builtin_inff()) : 0ull;
+}
+__device__ __forceinline__ unsigned long long stats_add(unsigned long long a, unsigned long long b, int f) {
+  if (f < STATS_COUNTS) return (unsigned long long)((long long)a + (long long)b);
+  const double x = __longlong_as_double((long long)a), y = __longlong_as_double((long long)b);
+  return (unsigned long long)__double_as_longlong(f < STATS_RMAX ? x + y : stats_max(x, y));
+}
+// `n` records `stride` words apart, field f of each, folded in index order
+__device__ __forceinline__ unsigned long long stats_fold(const unsigned long long* p, int n, int stride, int f) {
+  unsigned long long acc = stats_zero(f);
+#pragma unroll 8
+  for (int i = 0; i < n; i++) acc = stats_add(acc, p[(size_t)i * stride], f);
+  return acc;
+}
+
+// The block's record from its waves' LDS images rec[NW][STATS_FIELDS][64], after a block
+// barrier: thread f < STATS_FIELDS folds field f of each wave's lanes in lane order, then the
+// waves in wave order, and stores the block's word (a plain vector store).
+template <int NW>
+__device__ __forceinline__ void stats_block_fold(const unsigned long long* rec, int tid, unsigned long long* out) {
+  if (tid >= STATS_FIELDS) return;
+  unsigned long long acc = stats_zero(tid);
+#pragma unroll
+  for (int w = 0; w < NW; w++) acc = stats_add(acc, stats_fold(rec + ((size_t)w * STATS_FIELDS + tid) * 64, 64, 1, tid), tid);
+  out[tid] = acc;
+}
+
+}  // namespace wk

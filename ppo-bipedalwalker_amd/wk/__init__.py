@@ -47,6 +47,7 @@ EXPORTS = [
     "wk_object_update", "wk_joint_step", "wk_body_order",
     "wk_net_param_count", "wk_num_params", "wk_format_weights_net", "wk_parse_weights_net",
     "wk_get_bootstrap_values", "wk_set_bootstrap_values",
+    "wk_policy_stats", "wk_update_stats_get",
 ]
 
 
@@ -73,7 +74,7 @@ class WkConfig(C.Structure):
         ("Minibatch", C.c_int), ("MinibatchGlobal", C.c_int), ("EnvOffset", C.c_int),
         ("RandomizeStart", C.c_int), ("RandomizeMaterial", C.c_int),
         ("LanesPerWalker", C.c_int), ("NetworkKernels", C.c_int),
-        ("ReturnsMode", C.c_int),
+        ("ReturnsMode", C.c_int), ("TargetKL", C.c_float),
     ]
 
 
@@ -154,6 +155,25 @@ class PpoArgs(C.Structure):
 class RolloutStats(C.Structure):
     _fields_ = [("reward_sum", C.c_double), ("episodes", C.c_int64), ("env_steps", C.c_int64),
                 ("fault_or", C.c_uint32), ("pad", C.c_int32)]
+
+
+class PpoStats(C.Structure):
+    """wk_ppo_stats: the current policy on the trajectory buffer (wk_policy_stats) / the last
+    per-epoch check of a TargetKL > 0 update (wk_update_stats_get)"""
+    _fields_ = [("samples", C.c_int64), ("skipped", C.c_int64), ("kl", C.c_double),
+                ("kl_k1", C.c_double), ("clip_fraction", C.c_double), ("ratio_max", C.c_double),
+                ("surrogate", C.c_double), ("value_loss", C.c_double),
+                ("explained_variance", C.c_double), ("epochs_run", C.c_int32),
+                ("stopped_early", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+# the statistics kernels' grids (csrc/wk_kernels.h): the built-in kernel runs at most
+# STATS_MAX_BLOCKS blocks of STATS_WAVES waves, each wave striding over the 16-row chunks; the
+# general kernel at most NET_MAX_BLOCKS one-wave blocks of equally many consecutive 16-row tiles
+STATS_MAX_BLOCKS, STATS_WAVES, NET_MAX_BLOCKS, STATS_ROWS = 512, 4, 1024, 16
 
 
 class Profile(C.Structure):
@@ -278,6 +298,8 @@ def load_library(path=None):
         "wk_parse_weights_net": (I, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, P]),
         "wk_get_bootstrap_values": (I, [P, P]),
         "wk_set_bootstrap_values": (I, [P, P]),
+        "wk_policy_stats": (I, [P, C.POINTER(PpoStats), P, P]),
+        "wk_update_stats_get": (I, [P, C.POINTER(PpoStats)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -675,6 +697,29 @@ class Engine:
         the next compute_returns / ppo_update recomputes the returns"""
         v = _f32(v, (self.n,))
         self._chk(self.lib.wk_set_bootstrap_values(self.h, _ptr(v)), "wk_set_bootstrap_values")
+
+    def policy_stats(self, per_sample=False):
+        """wk_policy_stats: the current actor and critic on every row of the trajectory buffer --
+        approximate KL to the collecting policy, clip fraction, largest ratio, surrogate, value
+        loss and explained variance as a dict; per_sample=True also returns the rows' fp32
+        log-densities [T, n, 4] and values [T, n] (skipped rows included)"""
+        st = PpoStats()
+        if not per_sample:
+            self._chk(self.lib.wk_policy_stats(self.h, C.byref(st), None, None), "wk_policy_stats")
+            return st.as_dict()
+        # (the buffer's valid horizon is the library's to know: room for the configured one)
+        lp = np.zeros((self.cfg.Horizon, self.n, 4), np.float32)
+        v = np.zeros((self.cfg.Horizon, self.n), np.float32)
+        self._chk(self.lib.wk_policy_stats(self.h, C.byref(st), _ptr(lp), _ptr(v)), "wk_policy_stats")
+        T = (st.samples + st.skipped) // self.n
+        return st.as_dict(), lp[:T], v[:T]
+
+    def update_stats(self):
+        """wk_update_stats_get: the last per-epoch check of the last ppo_update of a TargetKL > 0
+        context (with epochs_run and stopped_early) as a dict"""
+        st = PpoStats()
+        self._chk(self.lib.wk_update_stats_get(self.h, C.byref(st)), "wk_update_stats_get")
+        return st.as_dict()
 
     def ppo_update(self, epochs=0, minibatch=0, minibatch_global=0, update_index=0, sync=True):
         """Whole PPO update; returns the last minibatch's (critic, actor) diagnostics, or
