@@ -497,6 +497,9 @@ DEV V2 pick(const Poly<N>& p, int i) {
 // projection below MaxValue (index -1) the reference keeps Vector2.Zero and takes the
 // neighbours (index + 1) % N = 0 and Mod(index - 1, N) = N - 2.
 DEV uint32_t bsel(uint32_t m, float a, uint32_t b) { return (m & __float_as_uint(a)) | (~m & b); }
+DEV V2 vbsel(uint32_t m, V2 a, V2 b) {  // m all ones: a, zero: b
+  return mk(__uint_as_float(bsel(m, a.x, __float_as_uint(b.x))), __uint_as_float(bsel(m, a.y, __float_as_uint(b.y))));
+}
 template <int N, bool SAFE = false>
 DEV void significant_face(const Poly<N>& P, V2 n, V2& fa, V2& fb, V2& fmax) {
   float mind = FLT_MAX;
@@ -576,16 +579,26 @@ DEV void significant_face_ax(const Poly<N>& P, const EdgeAxes<N>& AX, V2 n, V2& 
 }
 // significant_face_ax through LDS (the pair mapping's contact faces): instead of carrying the
 // vertex, both neighbours and two axes through ten bit-select chains over the N vertices, the
-// lane writes its polygon and axes as N float4 records (x, y, axis x, axis y) into its own LDS
-// column rec[k * S] (S: the block's lanes, so a wave's 16-byte accesses hit distinct banks), finds
-// the first strict minimum's index, and reads the three records it needs.  The same index rule as
-// significant_face_ax: with no projection below MaxValue (index -1) the vertex is Vector2.Zero,
-// its neighbours are vertices 0 and N - 2 and its axes N - 1 and N - 2 (the wrapped indices).
+// lane writes its polygon and axes as N records (x, y, axis x, axis y) into its own LDS column,
+// finds the first strict minimum's index, and reads the three records it needs.  The records lie
+// as four one-word planes each, component c of record k at rec[(4 k + c) S] (S: the block's
+// lanes, so a wave's accesses are 64 consecutive words: no bank conflict): every word is stored
+// from the register it already sits in, two per ds_write2st64_b32.  (A float4 per record needed
+// four consecutive registers, which the x[] / y[] arrays are not: 2-4 copies per record.)
+// The same index rule as significant_face_ax: with no projection below MaxValue (index -1) the
+// vertex is Vector2.Zero, its neighbours are vertices 0 and N - 2 and its axes N - 1 and N - 2
+// (the wrapped indices).
 template <int N, int S>
-DEV void significant_face_lds(const Poly<N>& P, const EdgeAxes<N>& AX, V2 n, float4* rec, V2& fa,
+DEV void significant_face_lds(const Poly<N>& P, const EdgeAxes<N>& AX, V2 n, float* rec, V2& fa,
                               V2& fb, V2& fmax, V2& fdir) {
+  static_assert(S % 64 == 0, "the planes' stride in ds_write2st64_b32 units");
 #pragma unroll
-  for (int k = 0; k < N; k++) rec[k * S] = make_float4(P.x[k], P.y[k], AX.x[k], AX.y[k]);
+  for (int k = 0; k < N; k++) {
+    rec[(4 * k + 0) * S] = P.x[k];
+    rec[(4 * k + 1) * S] = P.y[k];
+    rec[(4 * k + 2) * S] = AX.x[k];
+    rec[(4 * k + 3) * S] = AX.y[k];
+  }
   float mind = FLT_MAX;
   int idx = -1;
 #pragma unroll
@@ -599,12 +612,17 @@ DEV void significant_face_lds(const Poly<N>& P, const EdgeAxes<N>& AX, V2 n, flo
   const int inx = idx == N - 1 ? 0 : idx + 1;      // vertex i + 1 (-1 -> 0)
   const int ipv = idx <= 0 ? idx + N - 1 : idx - 1;  // vertex and axis i - 1 (-1 -> N - 2)
   __builtin_amdgcn_wave_barrier();  // (the lane reads only its own column: no other lane's data)
-  const float4 re = rec[ie * S], rn = rec[inx * S], rp = rec[ipv * S];
-  const V2 sig = idx < 0 ? mk(0.0f, 0.0f) : mk(re.x, re.y);
-  const V2 va = mk(rn.x, rn.y);
-  const V2 vb = mk(rp.x, rp.y);
-  const V2 after = mk(-re.w, re.z);    // -(axis_i.y, -axis_i.x)
-  const V2 before = mk(rp.w, -rp.z);   // (axis_{i-1}.y, -axis_{i-1}.x)
+  const float* const re = rec + ie * (4 * S);
+  const float* const rn = rec + inx * (4 * S);
+  const float* const rp = rec + ipv * (4 * S);
+  const float re_x = re[0], re_y = re[S], re_ax = re[2 * S], re_ay = re[3 * S];
+  const float rn_x = rn[0], rn_y = rn[S];
+  const float rp_x = rp[0], rp_y = rp[S], rp_ax = rp[2 * S], rp_ay = rp[3 * S];
+  const V2 sig = idx < 0 ? mk(0.0f, 0.0f) : mk(re_x, re_y);
+  const V2 va = mk(rn_x, rn_y);
+  const V2 vb = mk(rp_x, rp_y);
+  const V2 after = mk(-re_ay, re_ax);    // -(axis_i.y, -axis_i.x)
+  const V2 before = mk(rp_ay, -rp_ax);   // (axis_{i-1}.y, -axis_{i-1}.x)
   const bool first = vdot(n, before) >= vdot(n, after);
   fa = first ? sig : va;
   fb = first ? vb : sig;
@@ -646,13 +664,14 @@ DEV int contact_clip(V2 ra, V2 rb, V2 rmax, V2 rd, V2 ia, V2 ib, V2 imax, V2 id,
                      V2& c0, V2& c1) {
   V2 rf = vsub(rb, ra);
   V2 iv = vsub(ib, ia);
-  if (fabsf(vdot(rf, normal)) > fabsf(vdot(iv, normal))) {  // selects, not a branch
-    V2 t;
-    t = ra; ra = ia; ia = t;
-    t = rb; rb = ib; ib = t;
-    t = rmax; rmax = imax; imax = t;
-    rd = id;
-  }
+  // the reference / incident swap as one bit select per word: written as an `if` it compiled to
+  // a branch whose two arms renamed the faces with sixteen register copies at the join
+  const uint32_t sw = fabsf(vdot(rf, normal)) > fabsf(vdot(iv, normal)) ? 0xffffffffu : 0u;
+  const V2 ra0 = ra, rb0 = rb;
+  ra = vbsel(sw, ia, ra); ia = vbsel(sw, ra0, ia);
+  rb = vbsel(sw, ib, rb); ib = vbsel(sw, rb0, ib);
+  rmax = vbsel(sw, imax, rmax);  // (the incident face's max vertex is not used)
+  rd = vbsel(sw, id, rd);
   rf = rd;  // Normalize(rb - ra)
   float offset = vdot(rf, ra);
   V2 p0 = mk(0.0f, 0.0f), p1 = mk(0.0f, 0.0f);
@@ -675,7 +694,7 @@ DEV int contact_clip(V2 ra, V2 rb, V2 rmax, V2 rd, V2 ia, V2 ib, V2 imax, V2 id,
 template <int NA, int NB, int S = 0>  // S > 0: both faces through LDS (one column, in turn)
 DEV int contact_points_ax(const Poly<NA>& A, const EdgeAxes<NA>& AXA, const Poly<NB>& B,
                           const EdgeAxes<NB>& AXB, V2 normal, V2& c0, V2& c1,
-                          float4* rec = nullptr) {
+                          float* rec = nullptr) {
   V2 ra, rb, rmax, rd, ia, ib, imax, id;
   if constexpr (S > 0) {
     significant_face_lds<NA, S>(A, AXA, normal, rec, ra, rb, rmax, rd);
@@ -720,12 +739,37 @@ DEV void floor_face_ax(V2 n, V2& fa, V2& fb, V2& fmax, V2& fdir) {
 }
 template <int NA, int S = 0>  // S > 0: A's face through LDS (significant_face_lds, column rec)
 DEV int contact_points_floor(const Poly<NA>& A, const EdgeAxes<NA>& AXA, V2 normal, V2& c0,
-                             V2& c1, float4* rec = nullptr) {
+                             V2& c1, float* rec = nullptr) {
   V2 ra, rb, rmax, rd, ia, ib, imax, id;
   if constexpr (S > 0) significant_face_lds<NA, S>(A, AXA, normal, rec, ra, rb, rmax, rd);
   else significant_face_ax(A, AXA, normal, ra, rb, rmax, rd);
   floor_face_ax(vneg(normal), ia, ib, imax, id);
   return contact_clip(ra, rb, rmax, rd, ia, ib, imax, id, normal, c0, c1);
+}
+
+// The two leg segments' 24 vertex coordinates to / from the lane's face column, in the column's
+// own layout (word j at r[j S]: the words significant_face_lds uses and no other lane's), each
+// stored from the register it sits in.  The waves of a block are not in step, so another wave
+// may write its face records while this one's legs are parked: the columns must not overlap.
+template <int S>
+DEV void park_legs_planes(const Poly<6>& lo, const Poly<6>& up, float* r) {
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    r[i * S] = lo.x[i];
+    r[(6 + i) * S] = lo.y[i];
+    r[(12 + i) * S] = up.x[i];
+    r[(18 + i) * S] = up.y[i];
+  }
+}
+template <int S>
+DEV void unpark_legs_planes(Poly<6>& lo, Poly<6>& up, const float* r) {
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    lo.x[i] = r[i * S];
+    lo.y[i] = r[(6 + i) * S];
+    up.x[i] = r[(12 + i) * S];
+    up.y[i] = r[(18 + i) * S];
+  }
 }
 
 template <int NA, int NB, bool SAFE = false>

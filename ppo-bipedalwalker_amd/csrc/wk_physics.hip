@@ -15,6 +15,14 @@
 // Arithmetic is restated op-for-op in IEEE fp32 with -ffp-contract=off so the
 // trajectories are bit-identical to the CPU oracle (MonoGame Vector2 semantics:
 // v / f == v * (1/f); rotation via (float)cos/sin of the double-promoted angle).
+
+// The rough-floor side kernels (build part 5, see below) keep the compiler's own form of the
+// rotation's Horner steps (wk_sincos_small.h): with the scalar-constant steps the rough quad
+// kernel measured 0.4-0.6 % slower at the 8,192-walker shard, with the plain steps and the other
+// copy cuts 0.3 % faster than before (profiles/copy_cuts_ab.txt).  The same FMAs either way.
+#if defined(WK_PHYS_PART) && WK_PHYS_PART == 5
+#define WK_SC_PLAIN_FMA 1
+#endif
 #include "wk_common.h"
 #include "wk_device.h"
 #include "wk_kernels.h"
@@ -227,7 +235,7 @@ DEV bool sat_split(const Poly<N>& A, const Poly<N>& B, int half, V2& normal, flo
 // negation (each from its own SAT axes), exchanged, then the clipping in both
 template <int N, int FS = 0>  // FS > 0: the face through LDS (significant_face_lds, column frec)
 DEV int contacts_split(const Poly<N>& P, const EdgeAxes<N>& AXP, int half, V2 normal, V2& c0,
-                       V2& c1, float4* frec = nullptr) {
+                       V2& c1, float* frec = nullptr) {
   V2 fa, fb, fm, fd;
   if constexpr (FS > 0) significant_face_lds<N, FS>(P, AXP, half ? vneg(normal) : normal, frec, fa, fb, fm, fd);
   else significant_face_ax(P, AXP, half ? vneg(normal) : normal, fa, fb, fm, fd);
@@ -290,7 +298,7 @@ DEV bool sat_floor_split(const Poly<6>& A, const Poly<4>& F, float mnx, float mn
 template <int NA, int NB, bool BSTATIC, bool TRACE, int L, bool GENERIC = false, int H = 1, int FS = 0>
 DEV void resolve_pair(Poly<NA>& A, Dyn& dA, const Mat& mA, Poly<NB>& B, Dyn& dB, const Mat& mB,
                       bool& colA, PairTraceDev* tr, int pi, int sub, RegionProf* rp = nullptr,
-                      uint32_t* ec = nullptr, float4* frec = nullptr) {
+                      uint32_t* ec = nullptr, float* frec = nullptr) {
   static_assert(H == 1 || (L == 1 && !GENERIC && NA == 6 && NB == (BSTATIC ? 4 : 6)),
                 "the quad split covers leg-leg and leg-floor pairs");
   static_assert(!BSTATIC || NB == 4, "the static body is the floor");
@@ -857,7 +865,8 @@ struct SideState {
 };
 
 // the legs' 24 vertex coordinates (NR = 6 records; NR = 4: the first 16 of them) to / from a
-// lane's float4 column (stride FS); see k_env_side
+// lane's float4 column (stride FS): the rough floor's own stash, see k_env_side.  (The flat
+// floor's kernel parks them in its face column's planes: park_legs_planes, wk_device.h.)
 template <int FS, int NR = 6>
 DEV void park_legs(const SideState& s, float4* r) {
   r[0 * FS] = make_float4(s.lo.x[0], s.lo.x[1], s.lo.x[2], s.lo.x[3]);
@@ -1005,7 +1014,7 @@ DEV void torso_step(SideState& s, const Mat& mb, float dt, float adx, float ady,
 template <bool TRACE, int Q, bool ROUGH = false, int TS = 1, int FS = 0>
 DEV void substep_side(SideState& s, const Mat& mp, const Mat& mb, float dt, float adx, float ady,
                       PairTraceDev* tr, int side, int half, RegionProf* rp, const float* ter = nullptr,
-                      float4* frec = nullptr) {
+                      float* frec = nullptr) {
   rp_mark(rp, RP_OTHER);
   Poly<4> fl;
   floor_poly(fl);
@@ -1203,8 +1212,8 @@ void k_env_side(EnvParams P, StepArgs A) {
   // [draw][walker of block]; the walker's lanes write the same values and read only its column
   constexpr int WPB = SIDE_BLOCK >> SH;
   __shared__ float ter_lds[ROUGH ? 11 * WPB : 1];
-  // the pair mapping's contact faces (significant_face_lds): 6 float4 records per lane,
-  // [record][lane of block] (24 KB per block; 2 blocks of 77 KB fit a CU's 160 KB -- not with the
+  // the pair mapping's contact faces (significant_face_lds): 6 records of 4 words per lane, as
+  // one-word planes [word][lane of block] (24 KB per block; 2 blocks of 77 KB fit a CU's 160 KB -- not with the
   // rough floor's terrain as well, which would leave one block per CU).  The quad mapping keeps
   // the select chains (its LDS build: bit-exact, 1 % slower, profiles/r04_face_lds_ab.txt)
   constexpr int FS = (Q == 1 && !ROUGH) ? SIDE_BLOCK : 0;
@@ -1248,8 +1257,10 @@ void k_env_side(EnvParams P, StepArgs A) {
     // made inside the loop): hoisted out of the loop they were ten loop-invariant VGPRs that
     // the register allocator kept in scratch
     const int tx = (int)lane_opaque(threadIdx.x);
-    float4* const frec = face_lds + (FS ? tx : 0);
-    float4* const stash = frec;
+    // the lane's column of one-word planes: words (float*)face_lds + j * FS + tx, j < 24, for the
+    // face records (significant_face_lds) and, over the policy, for the legs (park_legs_planes)
+    float* const frec = (float*)face_lds + (FS ? tx : 0);
+    float* const stash = frec;
     float* const wave_pol = pol_lds + (POLICY ? (tx >> 6) * 768 : 0);
     if (POLICY) {
       get_obs_side(s, side, obs);
@@ -1259,7 +1270,7 @@ void k_env_side(EnvParams P, StepArgs A) {
       // empty asm with a memory clobber keeps the compiler from forwarding the parked values in
       // registers across the section.  Pure data movement: bit-identical.
       if constexpr (SS != 0) {
-        park_legs<SS>(s, stash);
+        park_legs_planes<SS>(s.lo, s.up, stash);
         asm volatile("" ::: "memory");
       } else if constexpr (RS != 0) {
         park_legs<RS, 4>(s, rstash_lds + tx);
@@ -1287,7 +1298,7 @@ void k_env_side(EnvParams P, StepArgs A) {
       }
       if constexpr (SS != 0) {
         asm volatile("" ::: "memory");
-        unpark_legs<SS>(s, stash);
+        unpark_legs_planes<SS>(s.lo, s.up, stash);
       } else if constexpr (RS != 0) {
         asm volatile("" ::: "memory");
         unpark_legs<RS, 4>(s, rstash_lds + tx);
