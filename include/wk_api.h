@@ -462,6 +462,90 @@ int wk_ppo_update(wk_ctx* ctx, const wk_ppo_args* args, float* critic_diag, floa
 int wk_policy_stats(wk_ctx* ctx, wk_ppo_stats* out, float* logp_new /* T*n*4 or NULL */,
                     float* values_new /* T*n or NULL */);
 int wk_update_stats_get(wk_ctx* ctx, wk_ppo_stats* out);
+
+/* Policy evaluation (the engine's counterpart of the console's _bestDistance and last-episode
+ * average reward, Environment.cs:55-60,119): every walker of the context plays `episodes` COMPLETE
+ * episodes under the current actor -- its mean action, or sampled as wk_rollout samples -- and the
+ * results come back per episode and folded.
+ *
+ * Private state.  The evaluation steps its own copy of the walker records and its own Philox
+ * counter array (allocated on first use): the records start from the template, in the body order
+ * `start` names, the counters at rng_step0; start offsets and materials are the context's, and with
+ * scene props it steps a private copy of the props' current state.  Nothing a later call can
+ * observe changes: walker records, Philox counters, trajectory buffer (validity and bootstrap
+ * values included), episode and loss logs and the running episode sums, weights, Adam, the
+ * snapshot slot, the wk_profile totals, the episode-log clock.  It runs on both kernel families, is
+ * not bounded by Horizon, and with a communicator it is local to the rank (no collective).
+ *
+ * Per env-step four launches: the observations of the private records, the policy kernel (mean or
+ * act only; Philox step = the private counters), the context's own physics kernel in its
+ * caller-actions mode (every mapping, the rough floor, scene props; the actions go in unclipped and
+ * are clipped as for wk_step) and the accounting kernel.  A stochastic evaluation on a built-in
+ * context therefore uses the standalone policy kernel: the fused rollout's distribution, not its
+ * bits; on a NetworkKernels = 1 context the kernels are the rollout's own and the episodes are
+ * bit-equal to wk_rollout's from the same start.
+ *
+ * Episode end.  The kernels expose `done`, not Walker.Terminal, so the kind is derived from what
+ * the physics emits: final_x > 900.0f is WK_EVAL_SUCCESS (Environment.cs:113-117), else length >
+ * MaxTimesteps is WK_EVAL_TIME_LIMIT, else WK_EVAL_FELL -- a fall on the very step of the limit is
+ * reported as WK_EVAL_TIME_LIMIT.  distance starts at -inf and takes x where x > distance, so a NaN
+ * x is ignored.  After its last requested episode a walker's further steps are ignored.
+ *
+ * Stopping.  Every `poll` env-steps the host reads how many walkers are still running; the loop
+ * ends at the first poll that reads none, or at max_steps.  Slots not finished by then are
+ * WK_EVAL_UNFINISHED and zero otherwise; they are counted in `unfinished` and left out of every
+ * statistic.  With no finished episode the means, std, min and max are NaN (the integer length_min
+ * / length_max 0).  The fold is ordered (double sums, no floating-point atomics): the same records
+ * give the same bytes.
+ *
+ * What to expect.  A deterministic evaluation on the flat floor without RandomizeStart,
+ * RandomizeMaterial or RoughFloor plays n copies of one episode.  With start = 0 a deterministic
+ * walker's episodes k > 0 repeat its episode 0 (every reset returns to the same state);
+ * episodes > 1 is for stochastic runs.
+ *
+ * WK_ERR_ARG: episodes outside 0..WK_EVAL_MAX_EPISODES, start or stochastic outside 0..1, a
+ * negative max_steps or poll, a NULL out. */
+enum { WK_EVAL_MAX_EPISODES = 16 };
+enum wk_eval_end { WK_EVAL_FELL = 0, WK_EVAL_TIME_LIMIT = 1, WK_EVAL_SUCCESS = 2, WK_EVAL_UNFINISHED = 3 };
+
+typedef struct wk_eval_args {
+  int32_t episodes;    /* complete episodes per walker, 1..WK_EVAL_MAX_EPISODES; 0 -> 1 */
+  int32_t stochastic;  /* 0: action = the actor's mean; 1: sampled as wk_rollout samples (the policy kernel's act) */
+  int32_t start;       /* 0: every walker starts as after wk_reset(NULL) (post-reset body order);
+                          1: as at wk_create (episode-0 order) */
+  int32_t max_steps;   /* env-step cap; 0 -> episodes * (MaxTimesteps + 1), within which every walker finishes */
+  int32_t poll;        /* the host checks for completion every `poll` env-steps; 0 -> 32 */
+  uint32_t rng_step0;  /* stochastic: Philox step of every walker's first env-step */
+} wk_eval_args;
+
+typedef struct wk_eval_rec {   /* one episode slot, layout [episode k][walker e] */
+  float total_reward;  /* (float) of the double sum of its rewards, as wk_episode_rec */
+  int32_t length;      /* env-steps */
+  float distance;      /* largest torso x after any of its steps (before the auto-reset) */
+  float final_x;       /* torso x after its last step */
+  int32_t end;         /* wk_eval_end */
+  int32_t env;         /* EnvOffset + e */
+} wk_eval_rec;
+
+typedef struct wk_eval_stats {
+  int64_t episodes, unfinished, fell, timed_out, succeeded;  /* episodes: finished slots */
+  int64_t env_steps;              /* steps_run * n_env */
+  double reward_mean, reward_std /* population */, reward_min, reward_max;
+  double length_mean;  int32_t length_min, length_max;
+  double distance_mean, distance_max;
+  uint32_t fault_or;   int32_t steps_run;
+} wk_eval_stats;
+
+int wk_evaluate(wk_ctx* ctx, const wk_eval_args* args /* NULL = defaults */, wk_eval_stats* out,
+                wk_eval_rec* recs /* episodes * n_env or NULL */);
+/* The evaluation's own two kernels alone, on the private block as the context's last wk_evaluate
+ * left it (WK_ERR_STATE before one, and for a second timing of the same one): `reps` back-to-back launches of the fold (kernel pair) over
+ * that evaluation's records, then -- the running episodes started again -- `reps` of the
+ * accounting kernel on its last physics row, each burst between one HIP-event pair on the
+ * context's stream (mean duration per launch, as wk_time_gradient).  Touches nothing but that
+ * block. */
+int wk_evaluate_time(wk_ctx* ctx, int reps, double* step_ms, double* fold_ms);
+
 /* Train(Batch) on caller data: B samples, divisor b_div; grads_out (optional, WK_NPARAM)
  * receives the accumulated gradient before Adam. Returns skipped-sample count in *skipped. */
 int wk_train_batch(wk_ctx* ctx, int B, float b_div, const float* states, const float* actions,

@@ -122,6 +122,21 @@ namespace NEA.Walker
             Wk.Ok(ctx, Wk.wk_update_stats_get(ctx, out var s), "Exception while reading the update's statistics", log) ? s : null;
     }
 
+    // How good the policy is now (the counterpart of the console's _bestDistance and last-episode
+    // average reward, Environment.cs:55-60,119): every walker plays complete episodes under the
+    // current actor -- its mean action unless args.Stochastic -- on a private copy of the walker
+    // state, so a call between two updates changes nothing of the run.  records (optional) holds
+    // Episodes * wk_num_envs slots, layout [episode][walker].  null on failure, logged
+    public static class Evaluation
+    {
+        public static WkEvalStats? Run(IntPtr ctx, WkEvalArgs args = default, WkEvalRec[]? records = null, Action<string>? log = null) =>
+            Wk.Ok(ctx, Wk.wk_evaluate(ctx, ref args, out var s, records), "Exception while evaluating the policy", log) ? s : null;
+
+        // mean milliseconds per launch of the accounting kernel and of the fold, on the last Run's block
+        public static (double StepMs, double FoldMs)? KernelTimes(IntPtr ctx, int reps = 64, Action<string>? log = null) =>
+            Wk.Ok(ctx, Wk.wk_evaluate_time(ctx, reps, out var st, out var fo), "Exception while timing the evaluation kernels", log) ? (st, fo) : null;
+    }
+
     // Walker/Walker.cs:49-223 for walker `Index` of a context (a Walker owns no state of its own:
     // its bodies, torques, Collided flags and episode counter live in the context's records)
     public sealed class Walker

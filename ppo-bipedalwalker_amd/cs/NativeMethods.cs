@@ -132,6 +132,40 @@ public struct WkPpoStats
     public int EpochsRun, StoppedEarly;
 }
 
+// wk_evaluate: complete episodes under the current actor on a private copy of the walkers
+[StructLayout(LayoutKind.Sequential)]
+public struct WkEvalArgs
+{
+    public int Episodes;    // complete episodes per walker, 1..16 (0 = 1)
+    public int Stochastic;  // 0 = the actor's mean action, 1 = sampled as wk_rollout samples
+    public int Start;       // 0 = as after wk_reset(NULL), 1 = as at wk_create
+    public int MaxSteps;    // env-step cap (0 = Episodes * (MaxTimesteps + 1))
+    public int Poll;        // completion check every Poll env-steps (0 = 32)
+    public uint RngStep0;   // stochastic: Philox step of every walker's first env-step
+}
+
+// one episode slot of wk_evaluate, layout [episode][walker], End: 0 fell, 1 time limit, 2 success, 3 unfinished
+[StructLayout(LayoutKind.Sequential)]
+public struct WkEvalRec
+{
+    public float TotalReward;
+    public int Length;
+    public float Distance, FinalX;
+    public int End, Env;
+}
+
+[StructLayout(LayoutKind.Sequential)]
+public struct WkEvalStats
+{
+    public long Episodes, Unfinished, Fell, TimedOut, Succeeded, EnvSteps;
+    public double RewardMean, RewardStd, RewardMin, RewardMax;
+    public double LengthMean;
+    public int LengthMin, LengthMax;
+    public double DistanceMean, DistanceMax;
+    public uint FaultOr;
+    public int StepsRun;
+}
+
 [StructLayout(LayoutKind.Sequential)]
 public struct WkEpisodeRec
 {
@@ -221,6 +255,8 @@ public static class Wk
     [DllImport(Lib)] public static extern int wk_ppo_update(IntPtr ctx, ref WkPpoArgs args, out float criticDiag, out float actorDiag);
     [DllImport(Lib)] public static extern int wk_policy_stats(IntPtr ctx, out WkPpoStats stats, float[]? logpNew, float[]? valuesNew);
     [DllImport(Lib)] public static extern int wk_update_stats_get(IntPtr ctx, out WkPpoStats stats);
+    [DllImport(Lib)] public static extern int wk_evaluate(IntPtr ctx, ref WkEvalArgs args, out WkEvalStats stats, [Out] WkEvalRec[]? recs);
+    [DllImport(Lib)] public static extern int wk_evaluate_time(IntPtr ctx, int reps, out double stepMs, out double foldMs);
     [DllImport(Lib)] public static extern int wk_train_batch(IntPtr ctx, int B, float bDiv, float[] states, float[] actions, float[] logpOld, float[] returns, float[] adv, out float criticDiag, out float actorDiag, float[]? gradsOut, int applyAdam, out int skipped);
     [DllImport(Lib)] public static extern int wk_minibatch_gradient(IntPtr ctx, int B, float bDiv, float[] states, float[] actions, float[] logpOld, float[] returns, float[] adv, out float criticDiag, out float actorDiag, float[]? gradsOut, out int skipped);
 

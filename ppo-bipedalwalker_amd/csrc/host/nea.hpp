@@ -195,6 +195,25 @@ class PPOAgent {
       LogError(std::string("Exception while reading the update's statistics: ") + wk_last_error(ctx_));
     return s;
   }
+  // How good the policy is now (the counterpart of the console's _bestDistance and last-episode
+  // average reward, Environment.cs:55-60,119): every walker plays complete episodes under the
+  // current actor (its mean action unless args.stochastic) on a private copy of the walker state;
+  // records (optional) receives episodes * n slots, layout [episode][walker].  A zeroed record on
+  // failure
+  wk_eval_stats Evaluate(const wk_eval_args& args = wk_eval_args{}, std::vector<wk_eval_rec>* records = nullptr) {
+    wk_eval_stats s{};
+    if (records) records->assign((size_t)(args.episodes > 0 ? args.episodes : 1) * (size_t)wk_num_envs(ctx_), wk_eval_rec{});
+    if (wk_evaluate(ctx_, &args, &s, records ? records->data() : nullptr) != WK_OK)
+      LogError(std::string("Exception while evaluating the policy: ") + wk_last_error(ctx_));
+    return s;
+  }
+  // mean milliseconds per launch of (accounting kernel, fold) on the last Evaluate's block
+  std::pair<double, double> EvaluationKernelTimes(int reps = 64) {
+    double st = 0.0, fo = 0.0;
+    if (wk_evaluate_time(ctx_, reps, &st, &fo) != WK_OK)
+      LogError(std::string("Exception while timing the evaluation kernels: ") + wk_last_error(ctx_));
+    return {st, fo};
+  }
   std::vector<float> Save() {  // NeuralNetwork.Save order (flat)
     std::vector<float> p(NumParams());
     if (wk_get_weights(ctx_, p.data()) != WK_OK) LogError(wk_last_error(ctx_));

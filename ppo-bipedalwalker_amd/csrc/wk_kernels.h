@@ -239,6 +239,56 @@ hipError_t launch_net_stats(const StatsArgs& a, const NetDesc* nets, int act_row
 hipError_t launch_stats_finish(const unsigned long long* partial, int nblocks, StatsRec* out,
                                hipStream_t s);
 
+// Policy evaluation (wk_evaluate; wk_eval.hip).  The accounting kernel k_eval_step runs after
+// every env-step of the evaluation's private walker records, on SoA per-walker state; k_eval_fold
+// and k_eval_finish fold the [episodes][n] records with the discipline of wk_stats.h (integers and
+// doubles, lanes in lane order, waves in wave order, blocks in block order, no floating-point
+// atomics).  EvalRecDev's layout == wk_eval_rec (include/wk_api.h).
+struct EvalRecDev {
+  float total_reward;
+  int32_t length;
+  float distance;
+  float final_x;
+  int32_t end;
+  int32_t env;
+};
+enum : int { EVAL_FELL = 0, EVAL_TIME_LIMIT = 1, EVAL_SUCCESS = 2, EVAL_UNFINISHED = 3 };
+struct EvalArgs {
+  int n, episodes, env_offset, max_timesteps;
+  // one env-step's physics outputs (the scratch row)
+  const float* rew;          // [n]
+  const uint8_t* done;       // [n]
+  const float* pos;          // [n][2] torso position after the step, before any auto-reset
+  // per-walker running episode: reward sum, length, best x, episode index (== episodes: finished)
+  double* acc;               // [n]
+  int32_t* len;              // [n]
+  float* best;               // [n]
+  int32_t* epi;              // [n]
+  EvalRecDev* recs;          // [episodes][n]
+  uint32_t* running;         // walkers that still have an episode to finish
+};
+// the fold's record: EVAL_FIELDS 64-bit words -- counts and the length sum as integers, the sums
+// as doubles, then the extrema (a NaN reward stays in its minimum and maximum) and the fault OR
+enum : int {
+  EF_DONE = 0, EF_UNFIN, EF_FELL, EF_TIMED, EF_SUCC, EF_LEN,   // integer sums
+  EF_R, EF_RR, EF_DIST,                                        // double sums
+  EF_RMIN, EF_RMAX, EF_DMAX,                                   // double extrema
+  EF_LMIN, EF_LMAX,                                            // integer extrema
+  EF_FAULT,                                                    // OR
+  EVAL_FIELDS
+};
+// the fold's grid: at most EVAL_FOLD_MAX_BLOCKS blocks of EVAL_FOLD_BLOCK lanes, one lane per
+// walker (its episode slots in episode order), striding over the walkers: a block tile is
+// EVAL_FOLD_BLOCK walkers, one grid pass EVAL_FOLD_MAX_BLOCKS * EVAL_FOLD_BLOCK
+enum : int { EVAL_FOLD_BLOCK = 256, EVAL_FOLD_MAX_BLOCKS = 64 };
+int eval_fold_blocks(int n);
+hipError_t launch_eval_init(const EvalArgs& a, uint32_t* rng_t, uint32_t rng_step0, uint32_t* fault,
+                            hipStream_t s);
+hipError_t launch_eval_step(const EvalArgs& a, hipStream_t s);
+hipError_t launch_eval_fold(const EvalRecDev* recs, const uint32_t* fault, int n, int episodes,
+                            unsigned long long* partial /* [blocks][EVAL_FIELDS] */,
+                            unsigned long long* out /* [EVAL_FIELDS] */, hipStream_t s);
+
 // data collection: per-episode totals of a recorded rollout appended to the device log;
 // layout == wk_episode_rec (include/wk_api.h)
 struct EpisodeRecDev {

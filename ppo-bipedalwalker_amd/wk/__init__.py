@@ -47,7 +47,7 @@ EXPORTS = [
     "wk_object_update", "wk_joint_step", "wk_body_order",
     "wk_net_param_count", "wk_num_params", "wk_format_weights_net", "wk_parse_weights_net",
     "wk_get_bootstrap_values", "wk_set_bootstrap_values",
-    "wk_policy_stats", "wk_update_stats_get",
+    "wk_policy_stats", "wk_update_stats_get", "wk_evaluate", "wk_evaluate_time",
 ]
 
 
@@ -165,6 +165,43 @@ class PpoStats(C.Structure):
                 ("surrogate", C.c_double), ("value_loss", C.c_double),
                 ("explained_variance", C.c_double), ("epochs_run", C.c_int32),
                 ("stopped_early", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+EVAL_MAX_EPISODES = 16  # WK_EVAL_MAX_EPISODES
+EVAL_FELL, EVAL_TIME_LIMIT, EVAL_SUCCESS, EVAL_UNFINISHED = 0, 1, 2, 3  # enum wk_eval_end
+EVAL_STARTS = {"reset": 0, "create": 1}  # wk_eval_args.start
+# the evaluation fold's grid (csrc/wk_kernels.h): at most EVAL_FOLD_MAX_BLOCKS blocks of
+# EVAL_FOLD_BLOCK lanes, one lane per walker, striding over the walkers
+EVAL_FOLD_BLOCK, EVAL_FOLD_MAX_BLOCKS = 256, 64
+
+
+class EvalArgs(C.Structure):
+    _fields_ = [("episodes", C.c_int32), ("stochastic", C.c_int32), ("start", C.c_int32),
+                ("max_steps", C.c_int32), ("poll", C.c_int32), ("rng_step0", C.c_uint32)]
+
+
+class EvalRec(C.Structure):
+    _fields_ = [("total_reward", C.c_float), ("length", C.c_int32), ("distance", C.c_float),
+                ("final_x", C.c_float), ("end", C.c_int32), ("env", C.c_int32)]
+
+
+EVAL_DTYPE = np.dtype([("total_reward", np.float32), ("length", np.int32), ("distance", np.float32),
+                       ("final_x", np.float32), ("end", np.int32), ("env", np.int32)])
+assert EVAL_DTYPE.itemsize == C.sizeof(EvalRec) == 24
+
+
+class EvalStats(C.Structure):
+    """wk_eval_stats: the fold of an evaluation's finished episodes (wk_evaluate)"""
+    _fields_ = [("episodes", C.c_int64), ("unfinished", C.c_int64), ("fell", C.c_int64),
+                ("timed_out", C.c_int64), ("succeeded", C.c_int64), ("env_steps", C.c_int64),
+                ("reward_mean", C.c_double), ("reward_std", C.c_double),
+                ("reward_min", C.c_double), ("reward_max", C.c_double),
+                ("length_mean", C.c_double), ("length_min", C.c_int32), ("length_max", C.c_int32),
+                ("distance_mean", C.c_double), ("distance_max", C.c_double),
+                ("fault_or", C.c_uint32), ("steps_run", C.c_int32)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -300,6 +337,8 @@ def load_library(path=None):
         "wk_set_bootstrap_values": (I, [P, P]),
         "wk_policy_stats": (I, [P, C.POINTER(PpoStats), P, P]),
         "wk_update_stats_get": (I, [P, C.POINTER(PpoStats)]),
+        "wk_evaluate": (I, [P, C.POINTER(EvalArgs), C.POINTER(EvalStats), P]),
+        "wk_evaluate_time": (I, [P, I, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -720,6 +759,27 @@ class Engine:
         st = PpoStats()
         self._chk(self.lib.wk_update_stats_get(self.h, C.byref(st)), "wk_update_stats_get")
         return st.as_dict()
+
+    def evaluate(self, episodes=1, stochastic=False, start="reset", max_steps=0, poll=0, rng_step0=0,
+                 records=False):
+        """wk_evaluate: every walker plays `episodes` complete episodes under the current actor
+        (its mean action, or sampled with stochastic=True) on a private copy of the walker state --
+        nothing the training run can observe changes.  start: "reset" (as after reset()) or
+        "create" (episode-0 body order).  Returns the statistics as a dict; records=True also
+        returns the per-episode records, a structured array EVAL_DTYPE [episodes, n]"""
+        a = EvalArgs(int(episodes), int(bool(stochastic)), int(EVAL_STARTS.get(start, start)),
+                     int(max_steps), int(poll), int(rng_step0))
+        st = EvalStats()
+        rec = np.zeros((max(1, min(int(episodes), EVAL_MAX_EPISODES)), self.n), EVAL_DTYPE) if records else None
+        self._chk(self.lib.wk_evaluate(self.h, C.byref(a), C.byref(st), _ptr(rec)), "wk_evaluate")
+        return (st.as_dict(), rec) if records else st.as_dict()
+
+    def evaluate_time(self, reps=64):
+        """wk_evaluate_time: mean ms per launch of the evaluation's (accounting kernel, fold) on
+        the last evaluate()'s private block"""
+        s, f = C.c_double(), C.c_double()
+        self._chk(self.lib.wk_evaluate_time(self.h, int(reps), C.byref(s), C.byref(f)), "wk_evaluate_time")
+        return s.value, f.value
 
     def ppo_update(self, epochs=0, minibatch=0, minibatch_global=0, update_index=0, sync=True):
         """Whole PPO update; returns the last minibatch's (critic, actor) diagnostics, or
