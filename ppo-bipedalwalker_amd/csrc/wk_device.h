@@ -126,16 +126,31 @@ DEV void floor_poly(Poly<4>& f) {
   find_centroid(f);
 }
 
+// move, rotate, proj_minmax and pole_own_minmax take the vertices two at a time through
+// v_pk_add_f32 / v_pk_mul_f32 (the first pk_pairs<N>() vertices) and the rest one at a time: the
+// same IEEE operations per element either way, so the results are bit-identical.  Which form is
+// faster depends on the kernel (profiles/box_carry_ab.txt): the flat-floor pair kernel runs 1.4 %
+// faster per vertex (two waves per SIMD compete for the issue slots, where a packed f32 op costs
+// more than the two plain ones it replaces and needs a wait state before its dependent read: 610
+// more VALU per wave-substep, the waves' wait share 0.275 -> 0.178), the quad kernels 9 % slower
+// (one wave per SIMD: the extra instructions lengthen its one dependent chain).  wk_physics.hip
+// sets WK_VERTEX_PACKED 0 for build part 1 only.
+#ifndef WK_VERTEX_PACKED
+#define WK_VERTEX_PACKED 1
+#endif
+template <int N> constexpr int pk_pairs() { return WK_VERTEX_PACKED ? (N & ~1) : 0; }
+
 // Skeleton.Move (Skeleton.cs:76-85)
 template <int N>
 DEV void move(Poly<N>& p, V2 d) {
   const pf2 dx = {d.x, d.x}, dy = {d.y, d.y};
 #pragma unroll
-  for (int i = 0; i + 1 < N; i += 2) {
+  for (int i = 0; i < pk_pairs<N>(); i += 2) {
     const pf2 x = pf2{p.x[i], p.x[i + 1]} + dx, y = pf2{p.y[i], p.y[i + 1]} + dy;
     p.x[i] = x.x; p.x[i + 1] = x.y; p.y[i] = y.x; p.y[i + 1] = y.y;
   }
-  if (N & 1) { p.x[N - 1] = p.x[N - 1] + d.x; p.y[N - 1] = p.y[N - 1] + d.y; }
+#pragma unroll
+  for (int i = pk_pairs<N>(); i < N; i++) { p.x[i] = p.x[i] + d.x; p.y[i] = p.y[i] + d.y; }
   p.cx = p.cx + d.x;
   p.cy = p.cy + d.y;
 }
@@ -155,15 +170,15 @@ DEV void rotate(Poly<N>& p, float angle) {
   const pf2 cx = {p.cx, p.cx}, cy = {p.cy, p.cy}, z2 = {0.0f, 0.0f};
   const pf2 a11 = {m11, m11}, a12 = {m12, m12}, a21 = {m21, m21}, a22 = {m22, m22};
 #pragma unroll
-  for (int i = 0; i + 1 < N; i += 2) {
+  for (int i = 0; i < pk_pairs<N>(); i += 2) {
     const pf2 px = pf2{p.x[i], p.x[i + 1]} - cx, py = pf2{p.y[i], p.y[i + 1]} - cy;
     const pf2 tx = ((px * a11) + (py * a21)) + z2;
     const pf2 ty = ((px * a12) + (py * a22)) + z2;
     const pf2 x = tx + cx, y = ty + cy;
     p.x[i] = x.x; p.x[i + 1] = x.y; p.y[i] = y.x; p.y[i + 1] = y.y;
   }
-  if (N & 1) {
-    const int i = N - 1;
+#pragma unroll
+  for (int i = pk_pairs<N>(); i < N; i++) {
     float px = p.x[i] - p.cx, py = p.y[i] - p.cy;
     float tx = (px * m11) + (py * m21) + 0.0f;
     float ty = (px * m12) + (py * m22) + 0.0f;
@@ -222,18 +237,21 @@ DEV void project2(float ax, float ay, const Poly<NA>& A, const Poly<NB>& B, floa
 // same per-element operations as ax * x + ay * y (no FMA: -ffp-contract=off).  Measured
 // (bench A/B on one box): -2 % rollout time; Skeleton.Move / Rotate over vertex pairs
 // (move, rotate) another -0.7 %; packing per (x, y) pair instead cost +25 % (register
-// shuffles), packing the contact-face projections changed nothing.
+// shuffles), packing the contact-face projections changed nothing.  (Those figures are from
+// before the waves were paced; since then the pair kernel is faster per vertex, see
+// WK_VERTEX_PACKED above.)
 template <int N>
 DEV void proj_minmax(const Poly<N>& P, float ax, float ay, float& mn, float& mx) {
   float v[N];
   const pf2 a2 = {ax, ax}, b2 = {ay, ay};
 #pragma unroll
-  for (int i = 0; i + 1 < N; i += 2) {
+  for (int i = 0; i < pk_pairs<N>(); i += 2) {
     const pf2 q = (a2 * pf2{P.x[i], P.x[i + 1]}) + (b2 * pf2{P.y[i], P.y[i + 1]});
     v[i] = q.x;
     v[i + 1] = q.y;
   }
-  if (N & 1) v[N - 1] = ax * P.x[N - 1] + ay * P.y[N - 1];
+#pragma unroll
+  for (int i = pk_pairs<N>(); i < N; i++) v[i] = ax * P.x[i] + ay * P.y[i];
   mn = FLT_MAX; mx = -FLT_MAX;
 #pragma unroll
   for (int i = 0; i < N; i++) { mn = __builtin_fminf(mn, v[i]); mx = __builtin_fmaxf(mx, v[i]); }
@@ -256,11 +274,13 @@ DEV void pole_own_minmax(const Poly<6>& P, int I, float ax, float ay, float& mn,
   float v[6];
   const pf2 a2 = {ax, ax}, b2 = {ay, ay};
 #pragma unroll
-  for (int i = 0; i < 6; i += 2) {
+  for (int i = 0; i < pk_pairs<6>(); i += 2) {
     const pf2 q = (a2 * pf2{P.x[i], P.x[i + 1]}) + (b2 * pf2{P.y[i], P.y[i + 1]});
     v[i] = q.x;
     v[i + 1] = q.y;
   }
+#pragma unroll
+  for (int i = pk_pairs<6>(); i < 6; i++) v[i] = ax * P.x[i] + ay * P.y[i];
   if (I == 0 || I == 1) {
     mn = __builtin_fminf(__builtin_fminf(v[0], v[1]), v[2]);
     mx = __builtin_fmaxf(__builtin_fmaxf(v[3], v[4]), v[5]);

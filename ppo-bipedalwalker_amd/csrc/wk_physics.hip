@@ -23,6 +23,14 @@
 #if defined(WK_PHYS_PART) && WK_PHYS_PART == 5
 #define WK_SC_PLAIN_FMA 1
 #endif
+// The flat-floor pair kernels (build part 1, the headline rollout) take the polygons' vertices one
+// at a time instead of in v_pk_*_f32 pairs (wk_device.h, WK_VERTEX_PACKED): the same operations,
+// rollout -1.4 % at 65,536 walkers.  The quad kernels (part 8) measured 9 % slower that way and
+// keep the pairs; so do the rough-floor side kernels (part 5: its quad kernel +9 %, its pair
+// kernel -1.3 %, one part) and every other kernel (profiles/box_carry_ab.txt).
+#if defined(WK_PHYS_PART) && WK_PHYS_PART == 1 && !defined(WK_VERTEX_PACKED)
+#define WK_VERTEX_PACKED 0
+#endif
 #include "wk_common.h"
 #include "wk_device.h"
 #include "wk_kernels.h"
