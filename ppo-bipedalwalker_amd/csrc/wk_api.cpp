@@ -1420,18 +1420,17 @@ static uint64_t* xch_stamp_slot(wk_ctx* c) {
 }
 
 // How many block slabs of what size g's gradient kernel (*gi) writes, and g.partial = c->partial
-// sized for them.  Built-in kernels: nblocks slabs of SLAB floats followed by the stage-1 group
-// sums of the ordered reduction; general kernels (always k_net_grad): nblocks slabs of slabn floats.
-static int grad_slabs(wk_ctx* c, wk::GradArgs& g, int wpb, int* gi, int* nblocks) {
+// sized for them.  Built-in kernels: nblocks slabs of SLAB floats (the sequential kernel: one);
+// general kernels (always k_net_grad): nblocks slabs of slabn floats.
+static int grad_slabs(wk_ctx* c, wk::GradArgs& g, bool sequential, int* gi, int* nblocks) {
   size_t floats;
   *gi = wk::grad_impl_for(c->grad_impl, g.samples);
   if (c->general) {
     *nblocks = wk::net_grad_blocks(g.samples);
     floats = (size_t)*nblocks * c->slabn;
   } else {
-    *nblocks = wpb == 0 ? wk::ppo_grad_mfma_blocks(g.samples, *gi)
-                        : (g.samples + wpb * g.spw - 1) / (wpb * g.spw);
-    floats = ((size_t)*nblocks + wk::grad_reduce_groups(*nblocks)) * wk::SLAB;
+    *nblocks = sequential ? 1 : wk::ppo_grad_mfma_blocks(g.samples, *gi);
+    floats = (size_t)*nblocks * wk::SLAB;
   }
   if (ensure(c, &c->partial, &c->partial_bytes, sizeof(float) * floats)) return WK_ERR_HIP;
   g.partial = c->partial;
@@ -1461,17 +1460,18 @@ static wk::AdamArgs adam_args(wk_ctx* c) {  // advances the step count
 }
 
 // one minibatch: gradient kernel -> ordered block reduction -> [RCCL all-reduce] -> Adam
-// wpb == 0: the matrix-core kernel (wk_ppo_mfma.hip); wpb >= 1: the lane-per-neuron
-// kernel (wk_ppo.hip; wpb == 1 visits the samples in minibatch order)
-static int minibatch(wk_ctx* c, wk::GradArgs g, int wpb, int apply_adam) {
+// sequential: the lane-per-neuron kernel (wk_ppo.hip: one wave visits the samples in minibatch
+// order) instead of the kernel family's matrix-core kernel; the general networks have no
+// sequential kernel
+static int minibatch(wk_ctx* c, wk::GradArgs g, bool sequential, int apply_adam) {
   int gi, nblocks;
-  if (int r = grad_slabs(c, g, wpb, &gi, &nblocks)) return r;
+  if (int r = grad_slabs(c, g, sequential, &gi, &nblocks)) return r;
   wk::AdamArgs a{};
   if (apply_adam) a = adam_args(c);
   {
     ProfScope ps(c, PK_GRAD, 0, 2);
-    HIPCHK(c, wpb == 0 || c->general ? launch_grad_for(c, g, nblocks, gi)
-                                     : wk::launch_ppo_grad(g, wpb, nblocks, c->stream));
+    HIPCHK(c, sequential && !c->general ? wk::launch_ppo_grad(g, c->stream)
+                                        : launch_grad_for(c, g, nblocks, gi));
   }
   // the general networks: the ordered sum of k_net_grad's block slabs with Adam in the same
   // launch (one GPU: the exchanges refuse such a context)
@@ -1480,7 +1480,6 @@ static int minibatch(wk_ctx* c, wk::GradArgs g, int wpb, int apply_adam) {
     HIPCHK(c, wk::launch_net_reduce(c->partial, nblocks, c->np, c->grad, a, c->stream));
     return WK_OK;
   }
-  float* part2 = c->partial + (size_t)nblocks * wk::SLAB;
   // with a communicator (any size, also one rank) the collective path runs: reduction,
   // RCCL all-reduce, Adam -- a single-GPU test then covers the multi-GPU sequence
   const bool multi = c->comm != nullptr || c->host_ar != nullptr || c->ipc;
@@ -1502,15 +1501,13 @@ static int minibatch(wk_ctx* c, wk::GradArgs g, int wpb, int apply_adam) {
     HIPCHK(c, wk::launch_reduce_xch_adam(x, c->stream));
     return WK_OK;
   }
-  if (apply_adam && !multi) {  // one GPU: the last reduction stage applies Adam
-    ProfScope ps(c, PK_REDUCE, 0, 2);
-    HIPCHK(c, wk::launch_grad_reduce_adam(c->partial, nblocks, part2, c->grad, a, c->stream));
-    return WK_OK;
-  }
+  const bool fused_adam = apply_adam && !multi;  // one GPU: the reduction applies Adam
   {
     ProfScope ps(c, PK_REDUCE, 0, 2);
-    HIPCHK(c, wk::launch_grad_reduce(c->partial, nblocks, part2, c->grad, c->stream));
+    HIPCHK(c, wk::launch_grad_reduce(c->partial, nblocks, c->grad, fused_adam ? &a : nullptr,
+                                     c->stream));
   }
+  if (fused_adam) return WK_OK;
 
   if (multi) {
     ProfScope ps(c, PK_ALLRED, 0, 2);
@@ -1893,7 +1890,7 @@ int wk_time_gradient_ex(wk_ctx* c, int minibatch, int reps, int flags, double* m
   wk::GradArgs g = traj_grad_args(c, M, (float)(c->cfg.MinibatchGlobal > 0 ? c->cfg.MinibatchGlobal : M));
   g.pk = wk::perm_key(c->seed, 0u, 0u, pool);
   int gi, nblocks;
-  if (int r = grad_slabs(c, g, 0, &gi, &nblocks)) return r;
+  if (int r = grad_slabs(c, g, false, &gi, &nblocks)) return r;
   HIPCHK(c, launch_grad_for(c, g, nblocks, gi));  // warm
   // flags & 1: an event pair around EVERY launch (as profile level 2 times the update's
   // launches), the elapsed times summed -- the burst's per-launch event overhead is the
@@ -1965,13 +1962,12 @@ static int ppo_update_impl(wk_ctx* c, const wk_ppo_args* args) {
   const uint32_t pool = (uint32_t)((size_t)c->n * c->T_valid);
   const int nmb = (int)(pool / (uint32_t)M);  // remainder dropped (PPOAgent.cs:506)
   if (nmb <= 0) { SETERR(c, "minibatch %d larger than the pool %u", M, pool); return WK_ERR_ARG; }
-  const int wpb = 0;  // matrix cores
   wk::GradArgs g = traj_grad_args(c, M, (float)Mg);
   for (int e = 0; e < epochs; e++) {
     g.pk = wk::perm_key(c->seed, update, (uint32_t)e, pool);
     for (int j = 0; j < nmb; j++) {
       g.base = (uint32_t)j * (uint32_t)M;
-      int r = minibatch(c, g, wpb, 1);
+      int r = minibatch(c, g, false, 1);
       if (r) return r;
     }
     // TargetKL: the policy's distance from the one that collected the data, after every epoch
@@ -1988,7 +1984,8 @@ static int ppo_update_impl(wk_ctx* c, const wk_ppo_args* args) {
   return WK_OK;
 }
 
-static int batch_impl(wk_ctx* c, int wpb, int B, float b_div, const float* s, const float* a,
+// sequential: as minibatch (wk_train_batch: the reference's sequential sums)
+static int batch_impl(wk_ctx* c, bool sequential, int B, float b_div, const float* s, const float* a,
                       const float* lpo, const float* ret, const float* adv, float* cd, float* ad,
                       float* grads_out, int apply_adam, int* skipped) {
   if (!c || B <= 0 || !s || !a || !lpo || !ret || !adv) return WK_ERR_ARG;
@@ -2008,11 +2005,10 @@ static int batch_impl(wk_ctx* c, int wpb, int B, float b_div, const float* s, co
   g.base = 0;
   g.use_perm = 0;
   g.samples = B;
-  g.spw = B;  // wpb 1: one wave, samples in order (the reference's sequential sums)
   g.b_div = b_div;
   int r = xch_mark_t(c);
   if (r) return r;
-  r = minibatch(c, g, wpb, apply_adam);
+  r = minibatch(c, g, sequential, apply_adam);
   if (r) return r;
   std::vector<float> slab(c->slabn);
   HIPCHK(c, hipMemcpyAsync(slab.data(), c->grad, sizeof(float) * slab.size(), hipMemcpyDeviceToHost, c->stream));
@@ -2030,14 +2026,14 @@ int wk_train_batch(wk_ctx* c, int B, float b_div, const float* s, const float* a
                    const float* ret, const float* adv, float* cd, float* ad, float* grads_out,
                    int apply_adam, int* skipped) {
   DevGuard dg_(c);
-  return batch_impl(c, 1, B, b_div, s, a, lpo, ret, adv, cd, ad, grads_out, apply_adam, skipped);
+  return batch_impl(c, true, B, b_div, s, a, lpo, ret, adv, cd, ad, grads_out, apply_adam, skipped);
 }
 
 int wk_minibatch_gradient(wk_ctx* c, int B, float b_div, const float* s, const float* a,
                           const float* lpo, const float* ret, const float* adv, float* cd,
                           float* ad, float* grads_out, int* skipped) {
   DevGuard dg_(c);
-  return batch_impl(c, 0, B, b_div, s, a, lpo, ret, adv, cd, ad, grads_out, 0, skipped);
+  return batch_impl(c, false, B, b_div, s, a, lpo, ret, adv, cd, ad, grads_out, 0, skipped);
 }
 
 static int refuse_comm(wk_ctx* c) {

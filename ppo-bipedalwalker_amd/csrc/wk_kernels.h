@@ -101,7 +101,11 @@ struct GradArgs {
   int use_perm;
   PermKey pk;
   int samples;           // samples in this minibatch (local)
-  int spw;               // samples per wave
+  int spw;               // the sequential kernel's samples per wave (launch_ppo_grad sets it to
+                         // samples; no one else reads it).  It stays: without it every later
+                         // argument moves, and the compiler then regroups the scalar loads and
+                         // reschedules every gradient kernel instead of only changing offsets
+                         // (profiles/prune_update_path.txt)
   float b_div;           // divisor of dV / dmu (BatchSize / global minibatch)
   float std_;            // MathF.Exp(LogStandardDeviation)
   float lp_const;        // -ln(std) - ln(sqrt(2 pi))
@@ -125,7 +129,12 @@ hipError_t launch_policy(const EnvParams& P, const float* W, float lp_const, int
                          float* mean, float* act, float* logp, float* v, hipStream_t s);
 hipError_t launch_returns(int n, int T, int use_gae, float gamma, float lambda, const float* r,
                           const float* v, const uint8_t* d, float* ret, float* adv, hipStream_t s);
-hipError_t launch_ppo_grad(const GradArgs& g, int wpb, int nblocks, hipStream_t s);
+// the ordered reduction of a gradient launch's block slabs (wk_tail.h): groups of RG consecutive
+// slabs in order, then up to RG groups in order -- no gradient launch writes more slabs
+enum { RG = 16 };
+enum : int { GRAD_MAX_BLOCKS = RG * RG };
+// the sequential lane-per-neuron kernel: one slab
+hipError_t launch_ppo_grad(GradArgs g, hipStream_t s);
 hipError_t configure_device_kernels();  // dynamic-LDS attributes, current device (wk_create)
 hipError_t configure_mfma_kernels();
 // matrix-core gradient kernels: producer / consumer pairs (ws), tile-parallel teams of four
@@ -137,11 +146,9 @@ hipError_t launch_ppo_grad_mfma(const GradArgs& g, int nblocks, int impl, hipStr
 hipError_t launch_swizzle(const float* W, float* Wz, hipStream_t s);
 int mfma_image_floats();
 int ppo_grad_mfma_blocks(int samples, int impl);
-hipError_t launch_grad_reduce(const float* partial, int nblocks, float* part2, float* grad,
+// nblocks <= GRAD_MAX_BLOCKS slabs -> grad [SLAB]; adam: applied in the same launch, or null
+hipError_t launch_grad_reduce(const float* partial, int nblocks, float* grad, const AdamArgs* adam,
                               hipStream_t s);
-int grad_reduce_groups(int nblocks);
-hipError_t launch_grad_reduce_adam(const float* partial, int nblocks, float* part2, float* grad,
-                                   const AdamArgs& a, hipStream_t s);
 hipError_t launch_adam(const AdamArgs& a, hipStream_t s);
 
 // One-shot gradient exchange over peer-mapped (IPC) memory, fused with the ordered block

@@ -5,13 +5,12 @@
 // (NeuralNetwork.FeedForward, NeuralNetwork.cs:52-64), the per-dimension clipped ratio
 // gradient (PPOAgent.cs:248-326), and NeuralNetwork.FeedBack (NeuralNetwork.cs:67-82,
 // DenseLayer.FeedBack DenseLayer.cs:103-120, ActivationLayer.FeedBack
-// ActivationLayer.cs:18-21) accumulating dW/db.  Mapping: one wave per sample stream,
-// lane j = neuron j of every 64-wide layer; weights staged once per block in LDS in the
-// two orientations the forward and backward passes read (both conflict-free); per-wave
-// accumulators stay in VGPRs; waves fold into one LDS slab in wave order, blocks write
-// partial slabs that k_grad_reduce sums in block order (no atomics: bit-reproducible).
-// Within a wave the samples are visited in minibatch order, so a single-wave launch
-// reproduces the reference's sequential accumulation exactly.
+// ActivationLayer.cs:18-21) accumulating dW/db.  Mapping: one block of one wave,
+// lane j = neuron j of every 64-wide layer; weights staged once in LDS in the two
+// orientations the forward and backward passes read (both conflict-free); the
+// accumulators stay in VGPRs and leave through one LDS slab, which k_grad_reduce_fused
+// takes like a matrix-core kernel's single block slab.  The wave visits the samples in
+// minibatch order, so it reproduces the reference's sequential accumulation exactly.
 #include "wk_common.h"
 #include "wk_kernels.h"
 #include "wk_mfma_layout.h"
@@ -41,6 +40,7 @@ enum : int {
   L_WEND = L_CB2 + 4
 };
 
+// (WPB, waves per block, is only ever 1; as a plain function it compiles to other machine code)
 template <int WPB>
 __global__ __launch_bounds__(64 * WPB) void k_ppo_grad(GradArgs g) {
   extern __shared__ float lds[];
@@ -253,48 +253,6 @@ __global__ __launch_bounds__(64 * WPB) void k_ppo_grad(GradArgs g) {
   for (int i = threadIdx.x; i < SLAB; i += 64 * WPB) out[i] = slab[i];
 }
 
-// Deterministic two-level sum of the block slabs (fixed association, no atomics):
-// stage 1 folds groups of RG consecutive slabs (all RG loads issued before the ordered
-// adds, so the chain is one memory latency, not RG); stage 2 folds the groups in order.
-// (RG, QB, adam_apply and the one-launch job: wk_tail.h)
-__global__ void k_grad_reduce1(const float* __restrict__ partial, int nblocks, float* part2) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  const int g = blockIdx.y;
-  if (p >= SLAB) return;
-  const int b0 = g * RG;
-  float v[RG];
-#pragma unroll
-  for (int j = 0; j < RG; j++) v[j] = (b0 + j < nblocks) ? partial[(size_t)(b0 + j) * SLAB + p] : 0.0f;
-  float acc = 0.0f;
-#pragma unroll
-  for (int j = 0; j < RG; j++)
-    if (b0 + j < nblocks) acc = acc + v[j];
-  part2[(size_t)g * SLAB + p] = acc;
-}
-
-// stage 2: the groups in order; up to RG groups are loaded at once (one latency), more
-// fall back to a loop -- same association either way
-DEV float sum_groups(const float* __restrict__ part2, int ngroups, int p) {
-  if (ngroups <= RG) {
-    float v[RG];
-#pragma unroll
-    for (int g = 0; g < RG; g++) v[g] = g < ngroups ? part2[(size_t)g * SLAB + p] : 0.0f;
-    float acc = 0.0f;
-#pragma unroll
-    for (int g = 0; g < RG; g++)
-      if (g < ngroups) acc = acc + v[g];
-    return acc;
-  }
-  float acc = 0.0f;
-  for (int g = 0; g < ngroups; g++) acc = acc + part2[(size_t)g * SLAB + p];
-  return acc;
-}
-__global__ void k_grad_reduce2(const float* __restrict__ part2, int ngroups, float* grad) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= SLAB) return;
-  grad[p] = sum_groups(part2, ngroups, p);
-}
-
 DEV void adam_param(const AdamArgs& a, int p, float gr) { adam_apply(a, p, gr, a.m[p], a.v[p], a.W[p]); }
 
 // elementwise over all 6149 parameters
@@ -303,21 +261,12 @@ __global__ void k_adam(AdamArgs a) {
   if (p < NPARAM) adam_param(a, p, a.grad[p]);
 }
 
-// single-GPU minibatch tail: the second reduction stage and Adam in one launch
-__global__ void k_grad_reduce2_adam(const float* __restrict__ part2, int ngroups, float* grad,
-                                    AdamArgs a) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= SLAB) return;
-  const float acc = sum_groups(part2, ngroups, p);
-  grad[p] = acc;
-  if (p < NPARAM) adam_param(a, p, acc);
-}
-
-// One-launch form of the two stages for nblocks <= RG * RG, bit-identical association
-// (RG consecutive slabs in order, then the groups in order): a block is one job of wk_tail.h's
-// reduce_job (QB parameter quads; thread (group gi, quad qi) folds its group's RG slabs with
-// 16-byte loads, all issued before the ordered adds, and the 16 group sums are folded in order
-// through LDS).  ADAM: the single-GPU tail applies Adam as well.
+// Deterministic two-level sum of the block slabs in one launch (fixed association, no atomics:
+// RG consecutive slabs in order, then the groups in order), for up to GRAD_MAX_BLOCKS slabs: a
+// block is one job of wk_tail.h's reduce_job (QB parameter quads; thread (group gi, quad qi)
+// folds its group's RG slabs with 16-byte loads, all issued before the ordered adds -- one memory
+// latency, not RG -- and the 16 group sums are folded in order through LDS).  ADAM: the
+// single-GPU tail applies Adam as well.
 template <bool ADAM>
 __global__ __launch_bounds__(RG * QB) void k_grad_reduce_fused(const float* __restrict__ partial,
                                                               int nblocks, float* grad, AdamArgs a) {
@@ -428,47 +377,26 @@ __global__ void k_xavier(float* W, uint64_t seed) {
 // current device (called by wk_create after hipSetDevice)
 hipError_t configure_device_kernels() {
   hipError_t e = hipFuncSetAttribute((const void*)k_ppo_grad<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute((const void*)k_ppo_grad<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (e == hipSuccess) e = configure_mfma_kernels();
   return e;
 }
 
-hipError_t launch_ppo_grad(const GradArgs& g, int wpb, int nblocks, hipStream_t s) {
-  const size_t lds = sizeof(float) * (L_WEND + SLAB + wpb * (64 * 4 + 24));
-  if (wpb == 1) {
-    hipLaunchKernelGGL((k_ppo_grad<1>), dim3(nblocks), dim3(64), lds, s, g);
-  } else {
-    hipLaunchKernelGGL((k_ppo_grad<4>), dim3(nblocks), dim3(256), lds, s, g);
-  }
+// the sequential kernel: one block of one wave, the whole minibatch in order
+hipError_t launch_ppo_grad(GradArgs g, hipStream_t s) {
+  const size_t lds = sizeof(float) * (L_WEND + SLAB + 64 * 4 + 24);
+  g.spw = g.samples;
+  hipLaunchKernelGGL((k_ppo_grad<1>), dim3(1), dim3(64), lds, s, g);
   return hipGetLastError();
 }
-hipError_t launch_grad_reduce(const float* partial, int nblocks, float* part2, float* grad,
+// adam: the single-GPU tail's Adam in the same launch, or null (grad only)
+hipError_t launch_grad_reduce(const float* partial, int nblocks, float* grad, const AdamArgs* adam,
                               hipStream_t s) {
-  if (nblocks <= RG * RG) {
-    hipLaunchKernelGGL(k_grad_reduce_fused<false>, dim3((SLAB / 4 + QB - 1) / QB), dim3(RG * QB), 0, s,
-                       partial, nblocks, grad, AdamArgs{});
-    return hipGetLastError();
-  }
-  const int ng = (nblocks + RG - 1) / RG;
-  hipLaunchKernelGGL(k_grad_reduce1, dim3((SLAB + 255) / 256, ng), dim3(256), 0, s, partial,
-                     nblocks, part2);
-  hipLaunchKernelGGL(k_grad_reduce2, dim3((SLAB + 255) / 256), dim3(256), 0, s, part2, ng, grad);
-  return hipGetLastError();
-}
-int grad_reduce_groups(int nblocks) { return (nblocks + RG - 1) / RG; }
-hipError_t launch_grad_reduce_adam(const float* partial, int nblocks, float* part2, float* grad,
-                                   const AdamArgs& a, hipStream_t s) {
-  if (nblocks <= RG * RG) {
-    hipLaunchKernelGGL(k_grad_reduce_fused<true>, dim3((SLAB / 4 + QB - 1) / QB), dim3(RG * QB), 0, s,
-                       partial, nblocks, grad, a);
-    return hipGetLastError();
-  }
-  const int ng = (nblocks + RG - 1) / RG;
-  hipLaunchKernelGGL(k_grad_reduce1, dim3((SLAB + 255) / 256, ng), dim3(256), 0, s, partial,
-                     nblocks, part2);
-  hipLaunchKernelGGL(k_grad_reduce2_adam, dim3((SLAB + 255) / 256), dim3(256), 0, s, part2, ng,
-                     grad, a);
+  if (nblocks > GRAD_MAX_BLOCKS) return hipErrorInvalidValue;
+  const dim3 grid((SLAB / 4 + QB - 1) / QB), block(RG * QB);
+  if (adam)
+    hipLaunchKernelGGL(k_grad_reduce_fused<true>, grid, block, 0, s, partial, nblocks, grad, *adam);
+  else
+    hipLaunchKernelGGL(k_grad_reduce_fused<false>, grid, block, 0, s, partial, nblocks, grad, AdamArgs{});
   return hipGetLastError();
 }
 // One-shot exchange (wk_comm_init_ipc): the minibatch's gradient all-reduce without a
@@ -614,7 +542,7 @@ int xch_blocks() { return (SLAB / 4 + QB - 1) / QB; }
 size_t xch_region_bytes() { return sizeof(float) * 2 * SLAB + sizeof(uint64_t) * XCH_FLAGS; }
 hipError_t launch_reduce_xch_adam(const XchArgs& x, hipStream_t s) {
   static_assert((SLAB / 4 + QB - 1) / QB <= XCH_FLAGS, "one flag per block");
-  if (x.nblocks > RG * RG) return hipErrorInvalidValue;  // (the gradient kernel caps at 256)
+  if (x.nblocks > GRAD_MAX_BLOCKS) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_reduce_xch_adam, dim3((SLAB / 4 + QB - 1) / QB), dim3(RG * QB), 0, s, x);
   return hipGetLastError();
 }

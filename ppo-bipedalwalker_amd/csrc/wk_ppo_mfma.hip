@@ -1289,13 +1289,13 @@ hipError_t configure_mfma_kernels() {
   return e;
 }
 
-// blocks of the kernel `impl` (resolved) for a minibatch; at most 256 (one per CU; the ordered
-// reduction's one-launch form and the IPC exchange take up to 256 slabs)
+// blocks of the kernel `impl` (resolved) for a minibatch; at most GRAD_MAX_BLOCKS (one per CU;
+// the ordered reduction and the IPC exchange take that many slabs)
 int ppo_grad_mfma_blocks(int samples, int impl) {
   const int chunks = (samples + 15) / 16;
   const int per = impl == GI_TP2 ? 2 : impl == GI_TP1 ? 1 : mf::WAVES;
   const int blocks = (chunks + per - 1) / per;
-  return blocks < 256 ? (blocks > 0 ? blocks : 1) : 256;
+  return blocks < GRAD_MAX_BLOCKS ? (blocks > 0 ? blocks : 1) : GRAD_MAX_BLOCKS;
 }
 
 hipError_t launch_ppo_grad_mfma(const GradArgs& g, int nblocks, int impl, hipStream_t s) {

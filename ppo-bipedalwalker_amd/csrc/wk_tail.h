@@ -14,8 +14,9 @@
 
 namespace wk {
 
-enum { RG = 16 };
 enum { QB = 16 };  // parameter quads per job (RG x QB threads; 16 timed best of 4 / 8 / 16)
+// a job's thread rows are its groups: RG of them (gi below), RG slabs each (RG: wk_kernels.h)
+static_assert(GRAD_MAX_BLOCKS == RG * RG, "the one-launch reduction covers every gradient launch");
 
 // DenseLayer.Adam (DenseLayer.cs:125-159) for one parameter, from its current m, v, w
 // (WT: the stores written through, see st_f)
@@ -33,7 +34,7 @@ __device__ __forceinline__ void adam_apply(const AdamArgs& a, int p, float gr, f
   if (a.Wz) mf_scatter_param<WT>(a.Wz, p, w);
 }
 
-// One job of the one-launch reduction for nblocks <= RG * RG (thread t of 256: group gi = t / QB,
+// One job of the reduction for nblocks <= GRAD_MAX_BLOCKS (thread t of 256: group gi = t / QB,
 // quad qi = t % QB; gs: the job's [RG][QB] float4 LDS tile).  The caller's block meets the one
 // barrier inside whether or not it has a job (job < 0: barrier only).  ADAM: also Adam (a.W set).
 template <bool ADAM>

@@ -46,8 +46,8 @@ def fingerprints(so):
                     name, body = (m.groups()[-1] if m else None), []
                     continue
                 ins = line.strip()
-                if not ins or ins.startswith(";"):
-                    continue
+                if not ins or ins.startswith(";") or ins == "...":  # "...": elided zero padding
+                    continue                                       # up to the next symbol
                 ins = re.sub(r"//.*$", "", ins).strip()
                 ins = re.sub(r"<[^>]*>", "", ins)          # branch target labels
                 ins = re.sub(r"0x[0-9a-f]+\b", "IMM", ins) if ins.startswith("s_cbranch") or \

@@ -79,6 +79,24 @@ def test_every_gradient_kernel_vs_f64(wk, orc, monkeypatch, impl, B, skip_at):
     assert abs(cd - cd64) <= 1e-5 * (abs(cd64) + 1.0) and abs(ad - ad64) <= 1e-5 * (abs(ad64) + 1.0)
 
 
+@pytest.mark.parametrize("B", [3856, 4096])
+def test_reduction_group_edges_vs_f64(wk, orc, B):
+    """the one-launch ordered reduction (the only one) at its group edges, under the default kernel
+    choice (tp1: one 16-sample chunk per block): 3,856 samples = 241 slabs, 15 full groups of 16
+    and a group of one; 4,096 = 256 slabs, the cap of every gradient launch"""
+    ag = orc.Agent(seed=SEED)
+    eng = wk.Engine(4, seed=SEED)
+    assert eng.grad_kernel(B) == "k_ppo_grad_tp1"
+    eng.set_weights(ag.params())
+    S, A, L, G, Ad = _batch(B, B)
+    g, cd, ad, sk = eng.minibatch_gradient(S, A, L, G, Ad)
+    og, ocd, oad, osk = ag.train_batch(S, A, L, G, Ad, b_div=B, apply_adam=False)
+    g64, asum, cd64, ad64, sk64 = ref64.train_batch_grad64(ag.params(), S, A, L, G, Ad, B)
+    _check_against_f64(g, og, g64, asum)
+    assert sk == osk == sk64 == 0
+    assert abs(cd - cd64) <= 1e-5 * (abs(cd64) + 1.0) and abs(ad - ad64) <= 1e-5 * (abs(ad64) + 1.0)
+
+
 def _check_against_f64(g, og, g64, asum):
     assert np.isfinite(g).all()
     scale = np.abs(g64).max()
