@@ -139,6 +139,25 @@ typedef struct wk_config {
                                shards would desert each other mid-exchange, so wk_comm_init,
                                wk_comm_init_host, wk_comm_ipc_handle and wk_comm_init_ipc return
                                WK_ERR_CONFIG on such a context.  Not part of the JSON document */
+  float MaxGradNorm;        /* 0 (default): off -- every minibatch launches what it always did.  > 0:
+                               per-network gradient-norm clipping in every Adam step (wk_ppo_update,
+                               wk_train_batch with apply_adam).  Critic = parameters [0, n_critic)
+                               of the flat vector, actor the rest (wk_num_params); per network, on
+                               the fp32 gradient Adam would have used (with a communicator: the
+                               sum over the ranks, so every rank scales alike): norm = sqrt(sum
+                               (double)g^2), coef = MaxGradNorm / (norm + 1e-6) in double, and the
+                               gradient is multiplied by (float)coef when norm is finite and coef
+                               < 1 (one fp32 product per parameter), else used as it is -- a
+                               non-finite norm is counted and not scaled.  +inf measures only.
+                               The minibatch tail becomes ordered reduction, then one launch
+                               that forms the norms and applies Adam; the gradient buffer,
+                               grads_out, the loss log and the diagnostics keep the unclipped
+                               values.  wk_grad_norms_get returns the record.  Negative or NaN is
+                               WK_ERR_CONFIG before a device is touched.  Works on both kernel
+                               families, with wk_comm_init and wk_comm_init_host; the IPC exchange
+                               fuses reduction, exchange and Adam in one launch, so
+                               wk_comm_ipc_handle and wk_comm_init_ipc return WK_ERR_CONFIG on
+                               such a context.  Not part of the JSON document */
 } wk_config;
 
 /* The host-only fields of the reference's JSON configuration (SerializableHyperparameters,
@@ -261,6 +280,22 @@ typedef struct wk_ppo_stats {
   int32_t epochs_run;         /* wk_update_stats_get only; 0 from wk_policy_stats */
   int32_t stopped_early;      /* wk_update_stats_get only: 1 when fewer epochs ran than asked */
 } wk_ppo_stats;
+
+/* The gradient norms of a MaxGradNorm > 0 context's Adam steps (wk_grad_norms_get), index 0 the
+ * critic, 1 the actor.  The device record is cleared at the start of every wk_ppo_update,
+ * wk_train_batch and wk_minibatch_gradient, so it describes the last such call.  The sum of
+ * squares has a fixed association that does not depend on the grid: the same inputs give the same
+ * bytes. */
+typedef struct wk_grad_norms {
+  int64_t steps;          /* Adam steps covered */
+  int64_t clipped[2];     /* steps whose gradient was scaled (scale < 1) */
+  int64_t nonfinite[2];   /* steps whose norm was not finite (not scaled) */
+  double norm_last[2];    /* the last step's norms */
+  double norm_max[2];     /* the largest norm; a NaN is ignored */
+  double norm_sum[2];     /* the sum of the finite norms */
+  float scale_last[2];    /* the last step's factors (1: not scaled) */
+  int32_t pad[2];
+} wk_grad_norms;
 
 /* one finished episode (data collection) */
 typedef struct wk_episode_rec {
@@ -462,6 +497,17 @@ int wk_ppo_update(wk_ctx* ctx, const wk_ppo_args* args, float* critic_diag, floa
 int wk_policy_stats(wk_ctx* ctx, wk_ppo_stats* out, float* logp_new /* T*n*4 or NULL */,
                     float* values_new /* T*n or NULL */);
 int wk_update_stats_get(wk_ctx* ctx, wk_ppo_stats* out);
+/* wk_grad_norms_get: the gradient-norm record of the last wk_ppo_update / wk_train_batch of a
+ * MaxGradNorm > 0 context.  It synchronises the stream (wk_ppo_update itself stays asynchronous).
+ * WK_ERR_STATE on a MaxGradNorm = 0 context, or when no Adam step ran since the record was last
+ * cleared; WK_ERR_ARG for NULLs.
+ * wk_set_learning_rate: Alpha from the next Adam step on, on every path (a host annealing it;
+ * wk_config.Alpha is otherwise copied at wk_create).  alpha must be finite and >= 0, else
+ * WK_ERR_ARG and nothing changes.  Not checkpointed, like the rest of the configuration.
+ * wk_get_learning_rate reads it back. */
+int wk_grad_norms_get(wk_ctx* ctx, wk_grad_norms* out);
+int wk_set_learning_rate(wk_ctx* ctx, float alpha);
+int wk_get_learning_rate(wk_ctx* ctx, float* alpha);
 
 /* Policy evaluation (the engine's counterpart of the console's _bestDistance and last-episode
  * average reward, Environment.cs:55-60,119): every walker of the context plays `episodes` COMPLETE

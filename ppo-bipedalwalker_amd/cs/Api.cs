@@ -122,6 +122,22 @@ namespace NEA.Walker
             Wk.Ok(ctx, Wk.wk_update_stats_get(ctx, out var s), "Exception while reading the update's statistics", log) ? s : null;
     }
 
+    // The size of the optimiser's steps (no counterpart in the reference): the per-network gradient
+    // norms of the last update's Adam steps on a MaxGradNorm > 0 context, and the learning rate a
+    // host may anneal between updates (Alpha is otherwise fixed at wk_create).  null / false on
+    // failure, logged like every other call
+    public static class Optimiser
+    {
+        public static WkGradNorms? GradNorms(IntPtr ctx, Action<string>? log = null) =>
+            Wk.Ok(ctx, Wk.wk_grad_norms_get(ctx, out var g), "Exception while reading the gradient norms", log) ? g : null;
+
+        public static bool SetLearningRate(IntPtr ctx, float alpha, Action<string>? log = null) =>
+            Wk.Ok(ctx, Wk.wk_set_learning_rate(ctx, alpha), "Exception while setting the learning rate", log);
+
+        public static float? LearningRate(IntPtr ctx, Action<string>? log = null) =>
+            Wk.Ok(ctx, Wk.wk_get_learning_rate(ctx, out var a), "Exception while reading the learning rate", log) ? a : null;
+    }
+
     // How good the policy is now (the counterpart of the console's _bestDistance and last-episode
     // average reward, Environment.cs:55-60,119): every walker plays complete episodes under the
     // current actor -- its mean action unless args.Stochastic -- on a private copy of the walker

@@ -44,6 +44,9 @@ public struct WkConfig
     // TargetKL: 0 = off, above 0 = after every epoch of wk_ppo_update the pass of wk_policy_stats runs over the trajectory buffer
     // and the remaining epochs are not run once its Kl exceeds the target (wk_update_stats_get returns the last check)
     public float TargetKL;
+    // MaxGradNorm: 0 = off, above 0 = every Adam step scales the critic's and the actor's summed gradient down to that L2 norm
+    // (float.PositiveInfinity measures only, wk_grad_norms_get returns the record, the IPC exchange refuses such a context)
+    public float MaxGradNorm;
 }
 
 // SerializableHyperparameters' host-only fields (Hyperparameters.cs:11-77)
@@ -130,6 +133,20 @@ public struct WkPpoStats
     public long Samples, Skipped;
     public double Kl, KlK1, ClipFraction, RatioMax, Surrogate, ValueLoss, ExplainedVariance;
     public int EpochsRun, StoppedEarly;
+}
+
+// wk_grad_norms_get: the gradient norms of a MaxGradNorm > 0 context's Adam steps, index 0 the critic, 1 the actor
+[StructLayout(LayoutKind.Sequential)]
+public unsafe struct WkGradNorms
+{
+    public long Steps;
+    public fixed long Clipped[2];
+    public fixed long Nonfinite[2];
+    public fixed double NormLast[2];
+    public fixed double NormMax[2];
+    public fixed double NormSum[2];
+    public fixed float ScaleLast[2];
+    public fixed int Pad[2];
 }
 
 // wk_evaluate: complete episodes under the current actor on a private copy of the walkers
@@ -255,6 +272,9 @@ public static class Wk
     [DllImport(Lib)] public static extern int wk_ppo_update(IntPtr ctx, ref WkPpoArgs args, out float criticDiag, out float actorDiag);
     [DllImport(Lib)] public static extern int wk_policy_stats(IntPtr ctx, out WkPpoStats stats, float[]? logpNew, float[]? valuesNew);
     [DllImport(Lib)] public static extern int wk_update_stats_get(IntPtr ctx, out WkPpoStats stats);
+    [DllImport(Lib)] public static extern int wk_grad_norms_get(IntPtr ctx, out WkGradNorms norms);
+    [DllImport(Lib)] public static extern int wk_set_learning_rate(IntPtr ctx, float alpha);
+    [DllImport(Lib)] public static extern int wk_get_learning_rate(IntPtr ctx, out float alpha);
     [DllImport(Lib)] public static extern int wk_evaluate(IntPtr ctx, ref WkEvalArgs args, out WkEvalStats stats, [Out] WkEvalRec[]? recs);
     [DllImport(Lib)] public static extern int wk_evaluate_time(IntPtr ctx, int reps, out double stepMs, out double foldMs);
     [DllImport(Lib)] public static extern int wk_train_batch(IntPtr ctx, int B, float bDiv, float[] states, float[] actions, float[] logpOld, float[] returns, float[] adv, out float criticDiag, out float actorDiag, float[]? gradsOut, int applyAdam, out int skipped);

@@ -119,7 +119,9 @@ namespace PPO {
 // (wk_get / wk_set_bootstrap_values); 0, the default, is the reference's arithmetic, and this
 // host, which trains on what wk_rollout recorded, needs no further call in either mode.
 // c.TargetKL > 0 ends an update's epochs once the approximate KL to the collecting policy passes
-// it (PPOAgent::UpdateStatistics returns the last check)
+// it (PPOAgent::UpdateStatistics returns the last check).
+// c.MaxGradNorm > 0 scales the critic's and the actor's gradient down to that L2 norm in every
+// Adam step (PPOAgent::GradNorms returns the update's record)
 struct Hyperparameters {
   wk_config c;
   Hyperparameters() { wk_config_defaults(&c); }
@@ -194,6 +196,24 @@ class PPOAgent {
     if (wk_update_stats_get(ctx_, &s) != WK_OK)
       LogError(std::string("Exception while reading the update's statistics: ") + wk_last_error(ctx_));
     return s;
+  }
+  // The per-network gradient norms of the last Train's Adam steps (c.MaxGradNorm > 0); a zeroed
+  // record on failure
+  wk_grad_norms GradNorms() {
+    wk_grad_norms g{};
+    if (wk_grad_norms_get(ctx_, &g) != WK_OK)
+      LogError(std::string("Exception while reading the gradient norms: ") + wk_last_error(ctx_));
+    return g;
+  }
+  // Alpha from the next Adam step on (a host annealing it; finite and >= 0)
+  void SetLearningRate(float alpha) {
+    if (wk_set_learning_rate(ctx_, alpha) != WK_OK)
+      LogError("Exception while setting the learning rate: alpha must be finite and >= 0");
+  }
+  float LearningRate() {
+    float a = 0.0f;
+    if (wk_get_learning_rate(ctx_, &a) != WK_OK) LogError(wk_last_error(ctx_));
+    return a;
   }
   // How good the policy is now (the counterpart of the console's _bestDistance and last-episode
   // average reward, Environment.cs:55-60,119): every walker plays complete episodes under the

@@ -74,6 +74,10 @@ struct wk_ctx {
   // TargetKL > 0: the last per-epoch check of the last wk_ppo_update (wk_update_stats_get)
   wk_ppo_stats upd_stats{};
   bool upd_stats_valid = false;
+  // MaxGradNorm > 0: the device record of the Adam steps' gradient norms (wk_grad_norms_get) and
+  // the steps launched since it was last cleared
+  wk::GradNormRec* gnorm = nullptr;
+  int64_t gnorm_steps = 0;
   // data collection (ConsoleRenderer.AddTotalEpisodeReward / AddCriticLoss / AddActorLoss)
   int collect = 1;
   uint32_t rollout_steps = 0;  // env-steps taken by wk_rollout so far (episode log clock)
@@ -301,6 +305,7 @@ void wk_config_defaults(wk_config* c) {
   c->NetworkKernels = 0;
   c->ReturnsMode = 0;
   c->TargetKL = 0.0f;
+  c->MaxGradNorm = 0.0f;
 }
 
 const char* wk_version(void) { return "wk 0.1 (gfx950)"; }
@@ -348,6 +353,8 @@ static int validate(const wk_config* c, std::string& why) {
     return bad("ReturnsMode must be 0 (the reference's returns) or 1 (chained GAE, bootstrap at the cut)");
   if (!std::isfinite(c->TargetKL) || c->TargetKL < 0.0f)
     return bad("TargetKL must be finite and >= 0 (0: no early stop)");
+  if (!(c->MaxGradNorm >= 0.0f))  // (a NaN compares false; +inf measures only)
+    return bad("MaxGradNorm must be >= 0 and not NaN (0: no clipping, inf: measure only)");
   if (c->Horizon <= 0) return bad("Horizon must be > 0");
   if (c->Minibatch < 0) return bad("Minibatch must be >= 0");
   if (c->LanesPerWalker != 0 && c->LanesPerWalker != 1 && c->LanesPerWalker != 2 &&
@@ -508,6 +515,7 @@ int wk_create(const wk_config* cfg, int device, int n_env, uint64_t seed, wk_ctx
       return fail(WK_ERR_HIP);
     }
   if (c.ReturnsMode == 1) ALLOC(x->vlast, sizeof(float) * n);
+  if (c.MaxGradNorm > 0.0f) ALLOC(x->gnorm, sizeof(wk::GradNormRec));
   x->ep_cap = (uint64_t)n * T;  // one rollout's worst case: every env-step ends an episode
   x->loss_cap = 1u << 16;
   ALLOC(x->ep_acc, sizeof(double) * n);
@@ -555,7 +563,8 @@ int wk_create(const wk_config* cfg, int device, int n_env, uint64_t seed, wk_ctx
       hipMemset(x->ep_acc, 0, sizeof(double) * n) != hipSuccess ||
       hipMemset(x->ep_len, 0, sizeof(int32_t) * n) != hipSuccess ||
       hipMemset(x->ep_rowcnt, 0, sizeof(uint32_t) * wk::episode_count_cells((int)n, T)) != hipSuccess ||
-      hipMemset(x->ep_count, 0, sizeof(uint64_t)) != hipSuccess) {
+      hipMemset(x->ep_count, 0, sizeof(uint64_t)) != hipSuccess ||
+      (x->gnorm && hipMemset(x->gnorm, 0, sizeof(wk::GradNormRec)) != hipSuccess)) {
     x->err = "initial upload failed";
     return fail(WK_ERR_HIP);
   }
@@ -1459,6 +1468,24 @@ static wk::AdamArgs adam_args(wk_ctx* c) {  // advances the step count
   return a;
 }
 
+// MaxGradNorm > 0: the norms of the summed gradient in c->grad, the scaled Adam step and the
+// device record in one launch (k_clip_adam), timed under the Adam slot
+static int clip_adam(wk_ctx* c, const wk::AdamArgs& a) {
+  ProfScope ps(c, PK_ADAM, 0, 2);
+  HIPCHK(c, wk::launch_clip_adam(a, c->np, c->net.critic.n_params, c->cfg.MaxGradNorm, c->gnorm,
+                                 c->stream));
+  c->gnorm_steps += 1;
+  return WK_OK;
+}
+// the record describes one wk_ppo_update / wk_train_batch / wk_minibatch_gradient: cleared,
+// stream-ordered, at its start
+static int gnorm_clear(wk_ctx* c) {
+  if (!c->gnorm) return WK_OK;
+  HIPCHK(c, hipMemsetAsync(c->gnorm, 0, sizeof(wk::GradNormRec), c->stream));
+  c->gnorm_steps = 0;
+  return WK_OK;
+}
+
 // one minibatch: gradient kernel -> ordered block reduction -> [RCCL all-reduce] -> Adam
 // sequential: the lane-per-neuron kernel (wk_ppo.hip: one wave visits the samples in minibatch
 // order) instead of the kernel family's matrix-core kernel; the general networks have no
@@ -1468,6 +1495,8 @@ static int minibatch(wk_ctx* c, wk::GradArgs g, bool sequential, int apply_adam)
   if (int r = grad_slabs(c, g, sequential, &gi, &nblocks)) return r;
   wk::AdamArgs a{};
   if (apply_adam) a = adam_args(c);
+  // MaxGradNorm > 0: the reduction leaves Adam to k_clip_adam, which runs on the summed gradient
+  const bool clip = apply_adam && c->gnorm != nullptr;
   {
     ProfScope ps(c, PK_GRAD, 0, 2);
     HIPCHK(c, sequential && !c->general ? wk::launch_ppo_grad(g, c->stream)
@@ -1476,9 +1505,12 @@ static int minibatch(wk_ctx* c, wk::GradArgs g, bool sequential, int apply_adam)
   // the general networks: the ordered sum of k_net_grad's block slabs with Adam in the same
   // launch (one GPU: the exchanges refuse such a context)
   if (c->general) {
-    ProfScope ps(c, PK_REDUCE, 0, 2);
-    HIPCHK(c, wk::launch_net_reduce(c->partial, nblocks, c->np, c->grad, a, c->stream));
-    return WK_OK;
+    {
+      ProfScope ps(c, PK_REDUCE, 0, 2);
+      HIPCHK(c, wk::launch_net_reduce(c->partial, nblocks, c->np, c->grad, clip ? wk::AdamArgs{} : a,
+                                      c->stream));
+    }
+    return clip ? clip_adam(c, a) : WK_OK;
   }
   // with a communicator (any size, also one rank) the collective path runs: reduction,
   // RCCL all-reduce, Adam -- a single-GPU test then covers the multi-GPU sequence
@@ -1501,7 +1533,7 @@ static int minibatch(wk_ctx* c, wk::GradArgs g, bool sequential, int apply_adam)
     HIPCHK(c, wk::launch_reduce_xch_adam(x, c->stream));
     return WK_OK;
   }
-  const bool fused_adam = apply_adam && !multi;  // one GPU: the reduction applies Adam
+  const bool fused_adam = apply_adam && !multi && !clip;  // one GPU: the reduction applies Adam
   {
     ProfScope ps(c, PK_REDUCE, 0, 2);
     HIPCHK(c, wk::launch_grad_reduce(c->partial, nblocks, c->grad, fused_adam ? &a : nullptr,
@@ -1529,6 +1561,7 @@ static int minibatch(wk_ctx* c, wk::GradArgs g, bool sequential, int apply_adam)
       HIPCHK(c, hipStreamSynchronize(c->stream));  // the host buffer is reused next minibatch
     }
   }
+  if (clip) return clip_adam(c, a);
   if (apply_adam) {
     ProfScope ps(c, PK_ADAM, 0, 2);
     HIPCHK(c, wk::launch_adam(a, c->stream));
@@ -1678,6 +1711,32 @@ int wk_update_stats_get(wk_ctx* c, wk_ppo_stats* out) {
     return WK_ERR_STATE;
   }
   *out = c->upd_stats;
+  return WK_OK;
+}
+
+int wk_grad_norms_get(wk_ctx* c, wk_grad_norms* out) {
+  DevGuard dg_(c);
+  if (!c || !out) return WK_ERR_ARG;
+  static_assert(sizeof(wk_grad_norms) == sizeof(wk::GradNormRec), "the device record is wk_grad_norms");
+  if (!c->gnorm || c->gnorm_steps == 0) {
+    SETERR(c, "wk_grad_norms_get: no Adam step was measured (MaxGradNorm = 0, or no step since the "
+              "record was cleared)");
+    return WK_ERR_STATE;
+  }
+  HIPCHK(c, hipMemcpyAsync(out, c->gnorm, sizeof(*out), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return WK_OK;
+}
+
+int wk_set_learning_rate(wk_ctx* c, float alpha) {
+  if (!c || !std::isfinite(alpha) || alpha < 0.0f) return WK_ERR_ARG;
+  c->cfg.Alpha = alpha;  // adam_args reads it at every step, on every path
+  return WK_OK;
+}
+
+int wk_get_learning_rate(wk_ctx* c, float* alpha) {
+  if (!c || !alpha) return WK_ERR_ARG;
+  *alpha = c->cfg.Alpha;
   return WK_OK;
 }
 
@@ -1954,6 +2013,7 @@ static int ppo_update_impl(wk_ctx* c, const wk_ppo_args* args) {
     if (r) return r;
   }
   if (int r = xch_mark_t(c)) return r;
+  if (int r = gnorm_clear(c)) return r;
   const int epochs = (args && args->epochs > 0) ? args->epochs : c->cfg.Epochs;
   const int M = (args && args->minibatch > 0) ? args->minibatch : c->cfg.Minibatch;
   int Mg = (args && args->minibatch_global > 0) ? args->minibatch_global : c->cfg.MinibatchGlobal;
@@ -2008,6 +2068,8 @@ static int batch_impl(wk_ctx* c, bool sequential, int B, float b_div, const floa
   g.b_div = b_div;
   int r = xch_mark_t(c);
   if (r) return r;
+  r = gnorm_clear(c);
+  if (r) return r;
   r = minibatch(c, g, sequential, apply_adam);
   if (r) return r;
   std::vector<float> slab(c->slabn);
@@ -2045,6 +2107,15 @@ static int refuse_comm(wk_ctx* c) {
   }
   if (!c->general) return WK_OK;
   SETERR(c, "the multi-GPU gradient exchange serves the built-in kernels only (NetworkKernels = 0)");
+  return WK_ERR_CONFIG;
+}
+
+// the IPC exchange applies Adam inside the launch that sums the ranks: no launch boundary at
+// which the norm of the summed gradient could be formed
+static int refuse_ipc_clip(wk_ctx* c) {
+  if (!c->gnorm) return WK_OK;
+  SETERR(c, "the IPC gradient exchange refuses a MaxGradNorm > 0 context: it fuses reduction, exchange "
+            "and Adam in one launch (wk_comm_init and wk_comm_init_host clip the summed gradient)");
   return WK_ERR_CONFIG;
 }
 
@@ -2094,6 +2165,7 @@ int wk_comm_ipc_handle(wk_ctx* c, uint8_t* handle) {
   DevGuard dg_(c);
   if (!c || !handle) return WK_ERR_ARG;
   if (int r = refuse_comm(c)) return r;
+  if (int r = refuse_ipc_clip(c)) return r;
   if (!c->xch) {
     // uncached (MTYPE UC) device memory: the peers read it over xGMI and this GPU writes it
     // through no cache; coarse-grained hipMalloc memory is the fallback where the driver cannot
@@ -2127,6 +2199,7 @@ int wk_comm_init_ipc(wk_ctx* c, int rank, int nranks, const uint8_t* handles) {
   DevGuard dg_(c);
   if (!c || !handles || nranks <= 0 || rank < 0 || rank >= nranks) return WK_ERR_ARG;
   if (int r = refuse_comm(c)) return r;
+  if (int r = refuse_ipc_clip(c)) return r;
   if (nranks > wk::XCH_MAX_RANKS) { SETERR(c, "the IPC exchange spans at most %d ranks", (int)wk::XCH_MAX_RANKS); return WK_ERR_ARG; }
   if (c->comm || c->host_ar || c->ipc) { SETERR(c, "the context already has an all-reduce"); return WK_ERR_STATE; }
   if (!c->xch) { SETERR(c, "wk_comm_ipc_handle first"); return WK_ERR_STATE; }

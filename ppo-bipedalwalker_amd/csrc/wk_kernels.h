@@ -150,6 +150,20 @@ int ppo_grad_mfma_blocks(int samples, int impl);
 hipError_t launch_grad_reduce(const float* partial, int nblocks, float* grad, const AdamArgs* adam,
                               hipStream_t s);
 hipError_t launch_adam(const AdamArgs& a, hipStream_t s);
+// MaxGradNorm > 0 (k_clip_adam, wk_ppo.hip): per-network gradient-norm clipping and Adam over
+// a.grad[0..np) of either kernel family, critic [0, n_critic) and actor [n_critic, np), and the
+// device record of the norms; layout == wk_grad_norms (include/wk_api.h)
+struct GradNormRec {
+  long long steps;
+  long long clipped[2];
+  long long nonfinite[2];
+  double norm_last[2], norm_max[2], norm_sum[2];
+  float scale_last[2];
+  int32_t pad[2];
+};
+static_assert(sizeof(GradNormRec) == 104, "GradNormRec is wk_grad_norms");
+hipError_t launch_clip_adam(const AdamArgs& a, int np, int n_critic, float max_norm, GradNormRec* rec,
+                            hipStream_t s);
 
 // One-shot gradient exchange over peer-mapped (IPC) memory, fused with the ordered block
 // reduction and Adam (wk_comm_init_ipc): rank r's exchange region is [2][SLAB] floats

@@ -261,6 +261,81 @@ __global__ void k_adam(AdamArgs a) {
   if (p < NPARAM) adam_param(a, p, a.grad[p]);
 }
 
+// MaxGradNorm > 0: per-network gradient-norm clipping, then Adam, for either kernel family
+// (a.grad[0..np): critic [0, n_critic), actor [n_critic, np)).  Per network
+//   norm = sqrt(sum (double)g^2), coef = MaxGradNorm / (norm + 1e-6)   (double)
+//   scale = (isfinite(norm) && coef < 1) ? (float)coef : 1;  Adam takes g * scale
+// (torch.nn.utils.clip_grad_norm_'s form; a non-finite norm passes the gradient as it is).
+// EVERY block forms both sums over the whole gradient itself -- it sits in the L2, 24 KiB for the
+// built-in networks and 280 KiB for the widest general ones -- so the launch has no inter-block
+// hand-off.  The association is fixed and independent of the grid: thread t of 256 takes elements
+// t, t + 256, ... of a network's segment in index order (CLIP_CB loads issued ahead of their adds:
+// one memory latency per batch, not per element), a wave folds its 64 partials by the xor
+// butterfly (every lane gets the same bits: the adds commute), and the four wave sums are added
+// in wave order.  Thread t of block b then applies Adam to parameter 256 b + t.  One lane of
+// block 0 updates the record with plain loads and stores: launches are stream-ordered.
+// (Batches of 32 with the two networks' first batches and butterflies interleaved measured slower,
+// 12.6 against 11.7 us per launch on the built-in networks: profiles/grad_clip.json has the latter.)
+enum : int { CLIP_CB = 16 };
+DEV double clip_sumsq(const float* __restrict__ g, int lo, int hi, int t) {
+  double s = 0.0;
+#pragma unroll 1
+  for (int i0 = lo + t; i0 < hi; i0 += CLIP_CB * 256) {
+    float v[CLIP_CB];
+#pragma unroll
+    for (int j = 0; j < CLIP_CB; j++) {
+      const int i = i0 + j * 256;
+      v[j] = i < hi ? g[i] : 0.0f;  // (past the end: + 0 leaves the sum as it is)
+    }
+#pragma unroll
+    for (int j = 0; j < CLIP_CB; j++) {
+      const double d = (double)v[j];
+      s = s + (d * d);
+    }
+  }
+#pragma unroll
+  for (int w = 1; w < 64; w <<= 1) s = s + __shfl_xor(s, w);
+  return s;
+}
+DEV float clip_scale(double norm, float max_norm) {
+  const double coef = (double)max_norm / (norm + 1e-6);
+  return (__builtin_isfinite(norm) && coef < 1.0) ? (float)coef : 1.0f;
+}
+__global__ __launch_bounds__(256) void k_clip_adam(AdamArgs a, int np, int n_critic, float max_norm,
+                                                   GradNormRec* rec) {
+  __shared__ double ws[2][4];
+  const int t = threadIdx.x, p = blockIdx.x * 256 + t;
+  // the Adam operands do not depend on the norms: their loads go out first
+  float g0 = 0.0f, m0 = 0.0f, v0 = 0.0f, w0 = 0.0f;
+  if (p < np) { g0 = a.grad[p]; m0 = a.m[p]; v0 = a.v[p]; w0 = a.W[p]; }
+  const double sc = clip_sumsq(a.grad, 0, n_critic, t);
+  const double sa = clip_sumsq(a.grad, n_critic, np, t);
+  if ((t & 63) == 0) { ws[0][t >> 6] = sc; ws[1][t >> 6] = sa; }
+  __syncthreads();
+  double norm[2];
+  float scale[2];
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    const double s = ((ws[k][0] + ws[k][1]) + ws[k][2]) + ws[k][3];
+    norm[k] = sqrt(s);
+    scale[k] = clip_scale(norm[k], max_norm);
+  }
+  if (p < np) adam_apply(a, p, g0 * (p < n_critic ? scale[0] : scale[1]), m0, v0, w0);
+  if (blockIdx.x == 0 && t == 0) {
+    rec->steps += 1;
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+      const bool fin = __builtin_isfinite(norm[k]);
+      if (scale[k] < 1.0f) rec->clipped[k] += 1;
+      if (!fin) rec->nonfinite[k] += 1;
+      rec->norm_last[k] = norm[k];
+      if (norm[k] > rec->norm_max[k]) rec->norm_max[k] = norm[k];  // (a NaN never compares above)
+      if (fin) rec->norm_sum[k] += norm[k];
+      rec->scale_last[k] = scale[k];
+    }
+  }
+}
+
 // Deterministic two-level sum of the block slabs in one launch (fixed association, no atomics:
 // RG consecutive slabs in order, then the groups in order), for up to GRAD_MAX_BLOCKS slabs: a
 // block is one job of wk_tail.h's reduce_job (QB parameter quads; thread (group gi, quad qi)
@@ -549,6 +624,12 @@ hipError_t launch_reduce_xch_adam(const XchArgs& x, hipStream_t s) {
 
 hipError_t launch_adam(const AdamArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_adam, dim3((NPARAM + 255) / 256), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+hipError_t launch_clip_adam(const AdamArgs& a, int np, int n_critic, float max_norm, GradNormRec* rec,
+                            hipStream_t s) {
+  if (np <= 0 || n_critic < 0 || n_critic > np || !rec) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_clip_adam, dim3((np + 255) / 256), dim3(256), 0, s, a, np, n_critic, max_norm, rec);
   return hipGetLastError();
 }
 hipError_t launch_normalize(float* x, int n, float eps, hipStream_t s) {

@@ -48,6 +48,7 @@ EXPORTS = [
     "wk_net_param_count", "wk_num_params", "wk_format_weights_net", "wk_parse_weights_net",
     "wk_get_bootstrap_values", "wk_set_bootstrap_values",
     "wk_policy_stats", "wk_update_stats_get", "wk_evaluate", "wk_evaluate_time",
+    "wk_grad_norms_get", "wk_set_learning_rate", "wk_get_learning_rate",
 ]
 
 
@@ -74,7 +75,7 @@ class WkConfig(C.Structure):
         ("Minibatch", C.c_int), ("MinibatchGlobal", C.c_int), ("EnvOffset", C.c_int),
         ("RandomizeStart", C.c_int), ("RandomizeMaterial", C.c_int),
         ("LanesPerWalker", C.c_int), ("NetworkKernels", C.c_int),
-        ("ReturnsMode", C.c_int), ("TargetKL", C.c_float),
+        ("ReturnsMode", C.c_int), ("TargetKL", C.c_float), ("MaxGradNorm", C.c_float),
     ]
 
 
@@ -168,6 +169,18 @@ class PpoStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class GradNorms(C.Structure):
+    """wk_grad_norms: the gradient norms of a MaxGradNorm > 0 context's Adam steps since the last
+    ppo_update / train_batch / minibatch_gradient began (index 0 the critic, 1 the actor)"""
+    _fields_ = [("steps", C.c_int64), ("clipped", C.c_int64 * 2), ("nonfinite", C.c_int64 * 2),
+                ("norm_last", C.c_double * 2), ("norm_max", C.c_double * 2),
+                ("norm_sum", C.c_double * 2), ("scale_last", C.c_float * 2), ("pad", C.c_int32 * 2)]
+
+    def as_dict(self):
+        return {k: (getattr(self, k) if k == "steps" else tuple(getattr(self, k)))
+                for k, _ in self._fields_ if k != "pad"}
 
 
 EVAL_MAX_EPISODES = 16  # WK_EVAL_MAX_EPISODES
@@ -339,6 +352,9 @@ def load_library(path=None):
         "wk_update_stats_get": (I, [P, C.POINTER(PpoStats)]),
         "wk_evaluate": (I, [P, C.POINTER(EvalArgs), C.POINTER(EvalStats), P]),
         "wk_evaluate_time": (I, [P, I, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "wk_grad_norms_get": (I, [P, C.POINTER(GradNorms)]),
+        "wk_set_learning_rate": (I, [P, F]),
+        "wk_get_learning_rate": (I, [P, fp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -759,6 +775,22 @@ class Engine:
         st = PpoStats()
         self._chk(self.lib.wk_update_stats_get(self.h, C.byref(st)), "wk_update_stats_get")
         return st.as_dict()
+
+    def grad_norms(self):
+        """wk_grad_norms_get: the per-network gradient norms of the Adam steps of the last
+        ppo_update / train_batch of a MaxGradNorm > 0 context as a dict (it synchronises)"""
+        g = GradNorms()
+        self._chk(self.lib.wk_grad_norms_get(self.h, C.byref(g)), "wk_grad_norms_get")
+        return g.as_dict()
+
+    def set_learning_rate(self, alpha):
+        """wk_set_learning_rate: Alpha from the next Adam step on (finite, >= 0)"""
+        self._chk(self.lib.wk_set_learning_rate(self.h, float(alpha)), "wk_set_learning_rate")
+
+    def get_learning_rate(self):
+        a = C.c_float()
+        self._chk(self.lib.wk_get_learning_rate(self.h, C.byref(a)), "wk_get_learning_rate")
+        return a.value
 
     def evaluate(self, episodes=1, stochastic=False, start="reset", max_steps=0, poll=0, rng_step0=0,
                  records=False):
