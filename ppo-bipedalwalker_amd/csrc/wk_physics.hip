@@ -661,11 +661,6 @@ DEV bool state_finite(const EnvState& s) {
   return acc == 0.0f;
 }
 
-// L lanes per walker (a "row"): the Gauss-Seidel chain runs replicated in every lane of
-// the row (bit-identical state), SAT axes are split one per lane (sat_row); lane 0 of
-// the row owns all stores.  L = 1 is the plain one-walker-per-lane mapping.
-// COUNT (one lane per walker, flat floor, given actions): the counting replay -- the same
-// physics with per-lane event counters summed into A.counts (SURVEY 8(d) F_counted).
 // Pacing of co-resident waves (k_env_side's pair mapping: two 4-wave blocks per CU; k_env_step:
 // two 64-lane blocks per SIMD).  The SIMD arbitrates VALU issue between its co-resident waves by
 // priority, then age (MI355X_MICROARCH.md, "Two waves per SIMD"): at equal priority the older
@@ -690,44 +685,55 @@ DEV void pace_partner(unsigned long long* pace, uint32_t seq, int k) {
   else __builtin_amdgcn_s_setprio(0);
 }
 
-template <bool POLICY, bool RECORD, bool TRACE, int L, bool ROUGH, bool COUNT = false>
-__global__ __launch_bounds__(64) WK_ENV_WPE void k_env_step(EnvParams P, StepArgs A) {
-  static_assert(!COUNT || (L == 1 && !POLICY && !TRACE), "counting replay");
-  const int tid = blockIdx.x * blockDim.x + threadIdx.x;
-  const int e = tid / L, sub = tid % L;
-  const int n = P.n_env;
-  if (e >= n) return;  // whole rows exit together
-  const bool leader = sub == 0;
-  __shared__ float pol_lds[(L == 16 && POLICY) ? 4 * 192 : 1];
-  // the walker's rough-floor heights 800 + Random.Next(0, 100), [draw][walker of block]:
-  // each lane writes and later reads only its own walker's column (no barrier needed)
-  __shared__ float ter_lds[ROUGH ? 11 * 64 : 1];
-  float* ter = ter_lds + (threadIdx.x / L);
-  if constexpr (ROUGH) {
-#pragma unroll 1
-    for (int i = 0; i < 11; i++)
-      ter[i * 64] = 800.0f + (float)terrain_draw(P.seed, (uint32_t)(P.env_offset + e), i);
-  }
-  EnvState s;
-  load_state(s, A.st, e, n);
-  const float dx = A.dxoff[e];
-  const MatConst mc = material(A.mat[e]);
-  const Mat mp{mc.inv_mass, 0.001f * mc.inv_mass, mc.restitution, mc.friction};
-  const Mat mb{mc.inv_mass, 0.0003f, mc.restitution, mc.friction};  // Walker.cs:168
+// What every env-step kernel's substeps take besides the state: the walker's part and torso
+// materials (Walker.cs:168) and the substep's time and gravity step, _acceleration * deltaTime
+struct StepConsts {
+  Mat mp, mb;
+  float dt, adx, ady;
+};
+DEV StepConsts step_consts(const EnvParams& P, int material_id) {
+  const MatConst mc = material(material_id);
   const float dt = P.dt_sub;
-  const float adx = 0.0f * dt, ady = 980.0f * dt;  // _acceleration * deltaTime
-  const uint32_t gid = (uint32_t)(P.env_offset + e);
-  uint32_t t = A.rng_t[e];
-  uint32_t fault = 0;
-  uint32_t ecnt[NEV];
-#pragma unroll
-  for (int i = 0; i < NEV; i++) ecnt[i] = 0u;
-  uint32_t* const ec = COUNT ? ecnt : nullptr;
+  return {{mc.inv_mass, 0.001f * mc.inv_mass, mc.restitution, mc.friction},
+          {mc.inv_mass, 0.0003f, mc.restitution, mc.friction}, dt, 0.0f * dt, 980.0f * dt};
+}
 
+// The outcome of a frame, after Walker.Update has set the position and s.terminal:
+// CalculateReward (Environment.cs:148-154) and the terminal checks (:106-117)
+DEV bool frame_outcome(const EnvParams& P, const EnvState& s, float& reward) {
+  reward = 0.0f;
+  float dX = s.posx - s.prevx;
+  float yb = s.body.y[1];
+  reward = reward + ((dX > 0.0f && ((yb / 500.0f) < 1.6f)) ? dX : 0.0f);
+  reward = reward - (((yb / 500.0f) > 1.65f) ? -0.1f : 0.0f);
+  bool terminal = false;
+  if (s.terminal || s.steps > P.max_timesteps) {
+    if (s.terminal) reward -= 40.0f;
+    terminal = true;
+  }
+  if (s.posx > 900.0f) {
+    reward += 80.0f;
+    terminal = true;
+  }
+  return terminal;
+}
+
+// The frame loop of Environment.Update (Environment.cs:64-180), A.k_steps env-steps of walker e
+// held in s: the one text of an env-step for k_env_step and k_env_scene (wk_scene.inc), which
+// keep their own preamble and epilogue and pass their substep of StepObjects as
+// step(PairTraceDev*), a force-inlined lambda (a plain one stays an out-of-line call).
+// PACE: the pacing call (not in the scene kernel); COUNT: the counting replay's counters ec.
+// k_env_side restates this loop in its own shape.
+template <bool POLICY, bool RECORD, bool TRACE, int L, bool COUNT, bool PACE, typename Step>
+DEV void env_frames(const EnvParams& P, const StepArgs& A, EnvState& s, int e, int sub, float dx,
+                    float* pol_lds, uint32_t& t, uint32_t& fault, uint32_t* ec, Step step) {
+  const int n = P.n_env;
+  const bool leader = sub == 0;
+  const uint32_t gid = (uint32_t)(P.env_offset + e);
 #pragma unroll 1
   for (int k = 0; k < A.k_steps; k++) {
     float a[4], lp[4], obs[12];
-    if (A.pace) pace_partner(A.pace, A.pace_seq, k);  // (lane 0 always holds a walker)
+    if (PACE && A.pace) pace_partner(A.pace, A.pace_seq, k);  // (lane 0 always holds a walker)
     if (POLICY) {
       get_obs(s, obs);
       float v = 0.0f;
@@ -771,7 +777,7 @@ __global__ __launch_bounds__(64) WK_ENV_WPE void k_env_step(EnvParams P, StepArg
       c = ac[3] - s.torque[3]; s.torque[3] = ac[3]; s.drll.w = s.drll.w + c * 5.0f;
     }
     // StepObjects
-    const uint32_t lf0 = ecnt[EV_AABB_LF], ll0 = ecnt[EV_SAT_LL];
+    const uint32_t lf0 = COUNT ? ec[EV_AABB_LF] : 0u, ll0 = COUNT ? ec[EV_SAT_LL] : 0u;
 #pragma unroll 1
     for (int it = 0; it < P.iterations; it++) {
       PairTraceDev* tr = nullptr;
@@ -780,43 +786,30 @@ __global__ __launch_bounds__(64) WK_ENV_WPE void k_env_step(EnvParams P, StepArg
         PairTraceDev z = {};
         *tr = z;
       }
-      substep<TRACE, L, ROUGH>(s, mp, mb, dt, adx, ady, tr, sub, ter, ec);
+      step(tr);
     }
-    if (COUNT) {
-      ecnt[EV_ENV_STEPS]++;
-      ecnt[EV_STEPS_LF] += ecnt[EV_AABB_LF] != lf0 ? 1u : 0u;
-      ecnt[EV_STEPS_SATLL] += ecnt[EV_SAT_LL] != ll0 ? 1u : 0u;
+    if constexpr (COUNT) {
+      ec[EV_ENV_STEPS]++;
+      ec[EV_STEPS_LF] += ec[EV_AABB_LF] != lf0 ? 1u : 0u;
+      ec[EV_STEPS_SATLL] += ec[EV_SAT_LL] != ll0 ? 1u : 0u;
     }
     // Walker.Update
     s.prevx = s.posx; s.prevy = s.posy;
     s.posx = s.body.cx; s.posy = s.body.cy;
     if (s.cbody || s.cllu || s.crlu) s.terminal = true;
-    // CalculateReward
-    float reward = 0.0f;
-    float dX = s.posx - s.prevx;
-    float yb = s.body.y[1];
-    reward = reward + ((dX > 0.0f && ((yb / 500.0f) < 1.6f)) ? dX : 0.0f);
-    reward = reward - (((yb / 500.0f) > 1.65f) ? -0.1f : 0.0f);
-    bool terminal = false;
-    if (s.terminal || s.steps > P.max_timesteps) {
-      if (s.terminal) reward -= 40.0f;
-      terminal = true;
-    }
-    if (s.posx > 900.0f) {
-      reward += 80.0f;
-      terminal = true;
-    }
+    float reward;
+    const bool terminal = frame_outcome(P, s, reward);
     if (!state_finite(s)) fault |= 1u;
     if (A.pos_out && leader) {
       A.pos_out[((size_t)k * n + e) * 2] = s.posx;
       A.pos_out[((size_t)k * n + e) * 2 + 1] = s.posy;
     }
-    if (terminal) {
+    if (terminal) {  // Walker.Reset (scene props keep their state and list positions)
       int ep = s.episodes + 1;
       make_template(s, dx);
       s.post = true;
       s.episodes = ep;
-      if (COUNT) ecnt[EV_RESETS]++;
+      if constexpr (COUNT) ec[EV_RESETS]++;
     }
     if (leader) {
       if (A.obs_out) {
@@ -834,6 +827,49 @@ __global__ __launch_bounds__(64) WK_ENV_WPE void k_env_step(EnvParams P, StepArg
     }
     t++;
   }
+}
+
+// L lanes per walker (a "row"): the Gauss-Seidel chain runs replicated in every lane of
+// the row (bit-identical state), SAT axes are split one per lane (sat_row); lane 0 of
+// the row owns all stores.  L = 1 is the plain one-walker-per-lane mapping.
+// COUNT (one lane per walker, given actions): the counting replay -- the same
+// physics with per-lane event counters summed into A.counts (SURVEY 8(d) F_counted).
+// The kernel's own text is the preamble (the terrain column, the state, the materials, the
+// counters) and the epilogue (the state, rng_t, the fault row, the counts' wave sums); the
+// env-steps between them are env_frames over substep<TRACE, L, ROUGH>.
+template <bool POLICY, bool RECORD, bool TRACE, int L, bool ROUGH, bool COUNT = false>
+__global__ __launch_bounds__(64) WK_ENV_WPE void k_env_step(EnvParams P, StepArgs A) {
+  static_assert(!COUNT || (L == 1 && !POLICY && !TRACE), "counting replay");
+  const int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  const int e = tid / L, sub = tid % L;
+  const int n = P.n_env;
+  if (e >= n) return;  // whole rows exit together
+  const bool leader = sub == 0;
+  __shared__ float pol_lds[(L == 16 && POLICY) ? 4 * 192 : 1];
+  // the walker's rough-floor heights 800 + Random.Next(0, 100), [draw][walker of block]:
+  // each lane writes and later reads only its own walker's column (no barrier needed)
+  __shared__ float ter_lds[ROUGH ? 11 * 64 : 1];
+  float* ter = ter_lds + (threadIdx.x / L);
+  if constexpr (ROUGH) {
+#pragma unroll 1
+    for (int i = 0; i < 11; i++)
+      ter[i * 64] = 800.0f + (float)terrain_draw(P.seed, (uint32_t)(P.env_offset + e), i);
+  }
+  EnvState s;
+  load_state(s, A.st, e, n);
+  const float dx = A.dxoff[e];
+  const StepConsts C = step_consts(P, A.mat[e]);
+  uint32_t t = A.rng_t[e];
+  uint32_t fault = 0;
+  uint32_t ecnt[NEV];
+#pragma unroll
+  for (int i = 0; i < NEV; i++) ecnt[i] = 0u;
+  uint32_t* const ec = COUNT ? ecnt : nullptr;
+
+  env_frames<POLICY, RECORD, TRACE, L, COUNT, true>(
+      P, A, s, e, sub, dx, pol_lds, t, fault, ec, [&](PairTraceDev* tr) __attribute__((always_inline)) {
+        substep<TRACE, L, ROUGH>(s, C.mp, C.mb, C.dt, C.adx, C.ady, tr, sub, ter, ec);
+      });
   if (leader) {
     store_state(s, A.st, e, n);
     A.rng_t[e] = t;
@@ -1247,6 +1283,7 @@ void k_env_side(EnvParams P, StepArgs A) {
   }
   SideState s;
   load_side(s, A.st, e, side);
+  // (step_consts restated: through the helper these kernels compile to other code)
   const MatConst mc = material(A.mat[e]);
   const Mat mp{mc.inv_mass, 0.001f * mc.inv_mass, mc.restitution, mc.friction};
   const Mat mb{mc.inv_mass, 0.0003f, mc.restitution, mc.friction};  // Walker.cs:168
@@ -1333,7 +1370,7 @@ void k_env_side(EnvParams P, StepArgs A) {
     s.posx = s.body.cx; s.posy = s.body.cy;
     const bool other_cup = pswap(s.cup ? 1.0f : 0.0f) != 0.0f;
     if (s.cbody || s.cup || other_cup) s.terminal = true;
-    float reward = 0.0f;
+    float reward = 0.0f;  // (frame_outcome restated, for the same reason)
     float dX = s.posx - s.prevx;
     float yb = s.body.y[1];
     reward = reward + ((dX > 0.0f && ((yb / 500.0f) < 1.6f)) ? dX : 0.0f);

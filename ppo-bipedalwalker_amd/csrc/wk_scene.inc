@@ -710,8 +710,9 @@ DEV void substep_scene(EnvState& s, const Mat& mp, const Mat& mb, float dt, floa
   }
 }
 
-// the one-lane env-step kernel with props (cf. k_env_step<POLICY, RECORD, TRACE, 1, false>);
-// A.props holds [n][S.pstride] prop state, staged in LDS for the launch
+// the one-lane env-step kernel with props: k_env_step's frame loop (env_frames, wk_physics.hip,
+// L = 1, no pacing, no counters) over substep_scene; its own part is the props -- A.props holds
+// [n][S.pstride] prop state, staged in LDS for the launch (with the boxes) and written back
 template <bool POLICY, bool RECORD, bool TRACE, bool ROUGH = false>
 __global__ __launch_bounds__(64) void k_env_scene(EnvParams P, StepArgs A, SceneDev S) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -734,101 +735,13 @@ __global__ __launch_bounds__(64) void k_env_scene(EnvParams P, StepArgs A, Scene
   EnvState s;
   load_state(s, A.st, e, n);
   const float dx = A.dxoff[e];
-  const MatConst mc = material(A.mat[e]);
-  const Mat mp{mc.inv_mass, 0.001f * mc.inv_mass, mc.restitution, mc.friction};
-  const Mat mb{mc.inv_mass, 0.0003f, mc.restitution, mc.friction};  // Walker.cs:168
-  const float dt = P.dt_sub;
-  const float adx = 0.0f * dt, ady = 980.0f * dt;
-  const uint32_t gid = (uint32_t)(P.env_offset + e);
+  const StepConsts C = step_consts(P, A.mat[e]);
   uint32_t t = A.rng_t[e];
   uint32_t fault = 0;
-#pragma unroll 1
-  for (int k = 0; k < A.k_steps; k++) {
-    float a[4], lp[4], obs[12];
-    if (POLICY) {
-      get_obs(s, obs);
-      float mean[4], v = 0.0f;
-      actor_mean(A.W, obs, mean);
-      sample_actions(P, A.lp_const, gid, t, mean, a, lp);
-      if (RECORD) {
-        v = critic_value(A.W, obs);
-        const size_t idx = (size_t)(A.t0 + k) * n + e;
-#pragma unroll
-        for (int i = 0; i < 12; i++) A.traj_s[idx * 12 + i] = obs[i];
-#pragma unroll
-        for (int d = 0; d < 4; d++) {
-          A.traj_a[idx * 4 + d] = a[d];
-          A.traj_lp[idx * 4 + d] = lp[d];
-        }
-        A.traj_v[idx] = v;
-      }
-    } else {
-#pragma unroll
-      for (int d = 0; d < 4; d++) a[d] = A.actions[((size_t)k * n + e) * 4 + d];
-    }
-    s.steps++;
-    float ac[4];
-#pragma unroll
-    for (int d = 0; d < 4; d++) ac[d] = clip1(a[d]);
-    {
-      float c;
-      c = ac[0] - s.torque[0]; s.torque[0] = ac[0]; s.dllu.w = s.dllu.w + c * 5.0f;
-      c = ac[1] - s.torque[1]; s.torque[1] = ac[1]; s.drlu.w = s.drlu.w + c * 5.0f;
-      c = ac[2] - s.torque[2]; s.torque[2] = ac[2]; s.dlll.w = s.dlll.w + c * 5.0f;
-      c = ac[3] - s.torque[3]; s.torque[3] = ac[3]; s.drll.w = s.drll.w + c * 5.0f;
-    }
-#pragma unroll 1
-    for (int it = 0; it < P.iterations; it++) {
-      PairTraceDev* tr = nullptr;
-      if (TRACE) {
-        tr = A.trace + ((size_t)e * P.iterations + it);
-        PairTraceDev z = {};
-        *tr = z;
-      }
-      substep_scene<TRACE, ROUGH>(s, mp, mb, dt, adx, ady, tr, S, col, ter);
-    }
-    s.prevx = s.posx; s.prevy = s.posy;
-    s.posx = s.body.cx; s.posy = s.body.cy;
-    if (s.cbody || s.cllu || s.crlu) s.terminal = true;
-    float reward = 0.0f;
-    float dX = s.posx - s.prevx;
-    float yb = s.body.y[1];
-    reward = reward + ((dX > 0.0f && ((yb / 500.0f) < 1.6f)) ? dX : 0.0f);
-    reward = reward - (((yb / 500.0f) > 1.65f) ? -0.1f : 0.0f);
-    bool terminal = false;
-    if (s.terminal || s.steps > P.max_timesteps) {
-      if (s.terminal) reward -= 40.0f;
-      terminal = true;
-    }
-    if (s.posx > 900.0f) {
-      reward += 80.0f;
-      terminal = true;
-    }
-    if (!state_finite(s)) fault |= 1u;
-    if (A.pos_out) {
-      A.pos_out[((size_t)k * n + e) * 2] = s.posx;
-      A.pos_out[((size_t)k * n + e) * 2 + 1] = s.posy;
-    }
-    if (terminal) {  // Walker.Reset: the props keep their state and list positions
-      int ep = s.episodes + 1;
-      make_template(s, dx);
-      s.post = true;
-      s.episodes = ep;
-    }
-    if (A.obs_out) {
-      get_obs(s, obs);
-#pragma unroll
-      for (int i = 0; i < 12; i++) A.obs_out[((size_t)k * n + e) * 12 + i] = obs[i];
-    }
-    if (A.rew_out) A.rew_out[(size_t)k * n + e] = reward;
-    if (A.done_out) A.done_out[(size_t)k * n + e] = terminal ? 1 : 0;
-    if (RECORD) {
-      const size_t idx = (size_t)(A.t0 + k) * n + e;
-      A.traj_r[idx] = reward;
-      A.traj_d[idx] = terminal ? 1 : 0;
-    }
-    t++;
-  }
+  env_frames<POLICY, RECORD, TRACE, 1, false, false>(
+      P, A, s, e, 0, dx, nullptr, t, fault, nullptr, [&](PairTraceDev* tr) __attribute__((always_inline)) {
+        substep_scene<TRACE, ROUGH>(s, C.mp, C.mb, C.dt, C.adx, C.ady, tr, S, col, ter);
+      });
   store_state(s, A.st, e, n);
   float* pout = A.props + (size_t)e * S.pstride;
 #pragma unroll 1

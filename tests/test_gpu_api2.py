@@ -4,6 +4,8 @@
   Environment.cs:70-89 records in the Trajectory (state before the step, UNCLIPPED action,
   per-dimension log-probability, reward, terminal) plus the value and the next state, so a
   single-instance C# host can train through PPOAgent.Train(Trajectory);
+* wk_step without actions -- the sampling kernels that record no trajectory, on every mapping,
+  both floors and with scene props, replayed through the oracle bit for bit;
 * wk_count_events -- the counting replay's physics events equal the oracle's per-substep
   bookkeeping (RigidBody.cs:66-96, Joint.cs:31-41) summed over the same env-steps, and the
   replay leaves the walkers in the rollout's final state bit for bit;
@@ -56,6 +58,50 @@ def test_step_sampled_equals_rollout(wk):
                      ("values", "values"), ("rewards", "rewards"), ("dones", "dones")):
         np.testing.assert_array_equal(out[key], tr[ref], err_msg=key)
     np.testing.assert_array_equal(a.get_state(), b.get_state())
+
+
+def _props(m):  # a box dropped on the torsos and a static hexagon among the feet
+    return [m(shape="Square", smooth=1, material="Wood", cx=150, cy=700, size=30, ay=980),
+            m(shape="Hexagon", material="Titanium", is_static=True, cx=200, cy=890, size=30)]
+
+
+@pytest.mark.parametrize("rough", [0, 1], ids=["flat", "rough"])
+@pytest.mark.parametrize("lanes,scene", [(1, False), (2, False), (4, False), (16, False), (1, True)],
+                         ids=["1", "2", "4", "16", "scene"])
+def test_unrecorded_policy_steps_replay_exactly(wk, orc, lanes, scene, rough):
+    """wk_step without actions: the policy kernels that keep no trajectory rows (no other test
+    runs them for the one- and 16-lane and the scene kernels).  A twin context's recorded steps
+    (wk_step_sampled: the same sampling) give the actions; the oracle replays them and must give
+    the observations, rewards, dones, final walkers and props bit for bit.  65 walkers: one lane
+    in the second wave; MaxTimesteps = 2: the third step resets every walker."""
+    n, k = 65, 3
+    cfg = dict(seed=SEED, RandomizeStart=1, RandomizeMaterial=1, MaxTimesteps=2, RoughFloor=rough,
+               LanesPerWalker=lanes)
+    ag = orc.Agent(seed=SEED)
+    eng, twin = wk.Engine(n, **cfg), wk.Engine(n, **cfg)
+    for x in (eng, twin):
+        x.set_weights(ag.params())
+        if scene:
+            x.set_scene(_props(wk.make_prop))
+    acts = twin.step_sampled(k)["actions"]
+    obs, rew, done, fault = eng.step(None, k=k)
+    envs = [orc.Env(dx=float(orc.env_offset(SEED, i)), material=int(orc.env_material(SEED, i)),
+                    rough=(SEED, i) if rough else None, props=_props(orc.make_prop) if scene else (),
+                    MaxTimesteps=2) for i in range(n)]
+    for i, e in enumerate(envs):
+        for t in range(k):
+            o, r, d = e.step(acts[t, i])
+            assert r == rew[t, i] and d == done[t, i], (i, t)
+            np.testing.assert_array_equal(o, obs[t, i], err_msg=f"env {i} t {t}")
+        for p in range(2 if scene else 0):
+            verts, st = e.prop(p)
+            v = eng.prop_view(i, p)
+            np.testing.assert_array_equal(v.vertex_array(), verts, err_msg=f"env {i} prop {p}")
+            got = np.array([v.centroid[0], v.centroid[1], v.linear_velocity[0], v.linear_velocity[1],
+                            v.angular_velocity, v.angle], F)
+            np.testing.assert_array_equal(got, st, err_msg=f"env {i} prop {p} state")
+    np.testing.assert_array_equal(eng.get_state(), np.stack([e.dump() for e in envs]))
+    assert done[k - 1].all() and not fault.any()
 
 
 def test_count_events_match_oracle_bookkeeping(wk, orc):
