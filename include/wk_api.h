@@ -158,6 +158,38 @@ typedef struct wk_config {
                                fuses reduction, exchange and Adam in one launch, so
                                wk_comm_ipc_handle and wk_comm_init_ipc return WK_ERR_CONFIG on
                                such a context.  Not part of the JSON document */
+  int LearnLogStd;          /* 0 (default): the policy's log-std is the constant LogStandardDeviation
+                               (or what wk_set_log_std last set); wk_ppo_update launches what it
+                               always did and stays asynchronous.  1: the one scalar log-std s,
+                               shared by the four action dimensions, is trained.  After every
+                               epoch's minibatches of wk_ppo_update, the last epoch included, the
+                               pass of wk_log_std_gradient runs over the whole trajectory buffer
+                               and its record is copied to the host (one stream synchronise per
+                               epoch: every kernel takes std by value at launch); the host takes
+                               one Adam step on s in double (Beta1, Beta2, AdamEpsilon widened;
+                               learning rate LogStdAlpha, or the context's current Alpha when that
+                               is 0) on grad = grad_surrogate - EntropyCoef, rounds s to float and
+                               clamps it to [LogStdMin, LogStdMax].  A non-finite gradient or a
+                               pass with no counted row takes no step.  Every later launch uses
+                               the new value: the next epoch, wk_rollout, wk_policy_sample,
+                               wk_step_sampled, wk_policy_stats, wk_evaluate; the trajectory's
+                               recorded log-densities stay the old policy's.  With TargetKL > 0
+                               the same pass yields that check's record (one pass per epoch; the
+                               order is pass, log-std step, stop decision).  MaxGradNorm does not
+                               touch s.  One GPU, like TargetKL: the four wk_comm_* initialisers
+                               return WK_ERR_CONFIG on such a context.  Anything but 0 or 1 is
+                               WK_ERR_CONFIG.  Not part of the JSON document, like the four below */
+  float LogStdAlpha;        /* 0 (default): the log-std step uses the context's current Alpha
+                               (wk_set_learning_rate).  > 0: its own learning rate.  Negative or
+                               non-finite is WK_ERR_CONFIG */
+  float EntropyCoef;        /* 0 (default).  The loss is -mean(surrogate) - EntropyCoef H with H = s +
+                               ln(2 pi e) / 2, the Gaussian's entropy per dimension, so the bonus
+                               adds -EntropyCoef to the gradient by s.  Finite and >= 0; > 0 with
+                               LearnLogStd = 0 is WK_ERR_CONFIG (with a fixed std the bonus is a
+                               constant) */
+  float LogStdMin;          /* -4 */
+  float LogStdMax;          /* 1.  Checked only when LearnLogStd = 1: -5 < LogStdMin <=
+                               LogStandardDeviation <= LogStdMax < 5, else WK_ERR_CONFIG */
 } wk_config;
 
 /* The host-only fields of the reference's JSON configuration (SerializableHyperparameters,
@@ -280,6 +312,32 @@ typedef struct wk_ppo_stats {
   int32_t epochs_run;         /* wk_update_stats_get only; 0 from wk_policy_stats */
   int32_t stopped_early;      /* wk_update_stats_get only: 1 when fewer epochs ran than asked */
 } wk_ppo_stats;
+
+/* The derivative of the clipped surrogate by the policy's scalar log-std s over the trajectory
+ * buffer (wk_log_std_gradient; the pass a LearnLogStd = 1 update runs after every epoch).  Per
+ * counted (row, dimension) entry, in fp32 as wk_ppo_stats and the gradient kernels form them:
+ * zz = ((act - mean) / std)^2, lp = lp_const - zz / 2, rr = expf(lp - logp_old), w = rr (partA +
+ * partB partC) the gradient kernels' selection of d surrogate / d lp; d lp / d s = zz - 1, so the
+ * entry's term is (double)w ((double)zz - 1).  Sums in double with the ordered fold of
+ * wk_policy_stats (no atomics: the same inputs give the same bytes); the host divides.  With no
+ * counted row the means are NaN; non-finite inputs of counted rows propagate. */
+typedef struct wk_log_std_grad {
+  int64_t samples, skipped; /* trajectory rows counted / dropped by the skip rule */
+  double grad_surrogate;    /* -mean over counted entries of w (zz - 1): d (-mean surrogate) / d s */
+  double grad;              /* grad_surrogate - EntropyCoef */
+  double z2_mean;           /* mean zz: 1 when std matches the actions' spread about the current mean */
+} wk_log_std_grad;
+
+/* The policy's log-std and the state of its Adam step (wk_get_log_std). */
+typedef struct wk_log_std_state {
+  float log_std, std;       /* current: s and expf(s), as every kernel launch takes them */
+  int32_t t, pad;           /* Adam step count of s */
+  double m, v;              /* its moments */
+  double entropy;           /* per dimension: log_std + 0.5 ln(2 pi e), double from the float */
+  double grad_last;         /* the gradient of the last wk_ppo_update's last step */
+  int64_t steps, clamped, nonfinite; /* of the last wk_ppo_update: steps taken, steps the clamp
+                               changed, passes whose gradient was not finite (no step) */
+} wk_log_std_state;
 
 /* The gradient norms of a MaxGradNorm > 0 context's Adam steps (wk_grad_norms_get), index 0 the
  * critic, 1 the actor.  The device record is cleared at the start of every wk_ppo_update,
@@ -508,6 +566,28 @@ int wk_update_stats_get(wk_ctx* ctx, wk_ppo_stats* out);
 int wk_grad_norms_get(wk_ctx* ctx, wk_grad_norms* out);
 int wk_set_learning_rate(wk_ctx* ctx, float alpha);
 int wk_get_learning_rate(wk_ctx* ctx, float* alpha);
+/* The policy's log-std (LearnLogStd, wk_log_std_state, wk_log_std_grad).
+ * wk_get_log_std: any context; on a LearnLogStd = 0 context t, m, v and the counters are 0.
+ * wk_set_log_std: any context (a host annealing the noise itself uses it with LearnLogStd = 0).
+ * log_std must be finite and inside (-5, 5), on a LearnLogStd = 1 context also inside [LogStdMin,
+ * LogStdMax]; else WK_ERR_ARG and nothing changes.  log_std, std = expf(log_std) and the
+ * log-density's constant are formed as wk_create forms them, so setting the create-time value
+ * reproduces the create-time bits; every later launch uses them.  It keeps m, v and t.  On a
+ * LearnLogStd = 0 context the value is configuration, like the learning rate: not checkpointed.
+ * wk_set_log_std_adam: the step's moments and count.  WK_ERR_STATE on a LearnLogStd = 0 context;
+ * WK_ERR_ARG for a non-finite m or v, a negative v or a negative t.
+ * wk_log_std_gradient: the pass alone, on any context with a trajectory, at the current log-std
+ * and weights, with wk_policy_stats' state rules and errors (stale returns are computed first;
+ * WK_ERR_STATE without a trajectory).  It synchronises the stream and changes nothing a later
+ * call can observe.
+ * wk_snapshot saves log_std, m, v and t and restores them on a LearnLogStd = 1 context (on a
+ * LearnLogStd = 0 context the value stays what wk_set_log_std made it).  A LearnLogStd = 1 context writes
+ * checkpoint version 6 (log_std, t, m, v after the network section) and loads only such files;
+ * a LearnLogStd = 0 context writes versions 4 / 5 byte for byte as before and refuses version 6. */
+int wk_get_log_std(wk_ctx* ctx, wk_log_std_state* out);
+int wk_set_log_std(wk_ctx* ctx, float log_std);
+int wk_set_log_std_adam(wk_ctx* ctx, double m, double v, int t);
+int wk_log_std_gradient(wk_ctx* ctx, wk_log_std_grad* out);
 
 /* Policy evaluation (the engine's counterpart of the console's _bestDistance and last-episode
  * average reward, Environment.cs:55-60,119): every walker of the context plays `episodes` COMPLETE

@@ -138,6 +138,24 @@ namespace NEA.Walker
             Wk.Ok(ctx, Wk.wk_get_learning_rate(ctx, out var a), "Exception while reading the learning rate", log) ? a : null;
     }
 
+    // The policy's exploration noise (LogStandardDeviation is a constant in the reference): the
+    // scalar log-std a LearnLogStd = 1 context trains after every epoch, or a host anneals itself
+    // with Set on any context; Gradient is the pass alone.  null / false on failure, logged
+    public static class LogStd
+    {
+        public static WkLogStdState? State(IntPtr ctx, Action<string>? log = null) =>
+            Wk.Ok(ctx, Wk.wk_get_log_std(ctx, out var s), "Exception while reading the log standard deviation", log) ? s : null;
+
+        public static bool Set(IntPtr ctx, float logStd, Action<string>? log = null) =>
+            Wk.Ok(ctx, Wk.wk_set_log_std(ctx, logStd), "Exception while setting the log standard deviation", log);
+
+        public static bool SetAdam(IntPtr ctx, double m, double v, int t, Action<string>? log = null) =>
+            Wk.Ok(ctx, Wk.wk_set_log_std_adam(ctx, m, v, t), "Exception while setting the log standard deviation's Adam state", log);
+
+        public static WkLogStdGrad? Gradient(IntPtr ctx, Action<string>? log = null) =>
+            Wk.Ok(ctx, Wk.wk_log_std_gradient(ctx, out var g), "Exception while reading the log standard deviation's gradient", log) ? g : null;
+    }
+
     // How good the policy is now (the counterpart of the console's _bestDistance and last-episode
     // average reward, Environment.cs:55-60,119): every walker plays complete episodes under the
     // current actor -- its mean action unless args.Stochastic -- on a private copy of the walker

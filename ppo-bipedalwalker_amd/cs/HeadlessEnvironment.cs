@@ -23,7 +23,7 @@ public sealed class Trajectory
 public sealed class HeadlessEnvironment : IDisposable
 {
     readonly IntPtr _ctx;
-    readonly WkConfig _cfg;
+    readonly WkConfigLogStd _cfg;
     readonly Action<string> _log;
     Trajectory _trajectory = new();
     float[] _state = new float[WkConst.Obs];
@@ -43,10 +43,10 @@ public sealed class HeadlessEnvironment : IDisposable
 
     // Environment(SpriteBatch, Renderer) (:39-51): Walker + CreateCreature + CreateFloor + agent
     public HeadlessEnvironment(ulong seed = 20250905, int device = 0, Action<string>? log = null,
-                               Func<WkConfig, WkConfig>? configure = null)
+                               Func<WkConfigLogStd, WkConfigLogStd>? configure = null)
     {
         _log = log ?? Console.Error.WriteLine;
-        var c = new WkConfig();
+        var c = new WkConfigLogStd();          // the whole wk_config
         Wk.wk_config_defaults(ref c);          // Hyperparameters.cs:83-121 defaults
         if (configure != null) c = configure(c);
         c.Horizon = c.MaxTimesteps + 1;        // one whole episode (terminal at steps > MaxTimesteps)

@@ -26,7 +26,8 @@ public static class WkConst
     public const int IpcHandleBytes = 128;  // WK_IPC_HANDLE_BYTES: IPC handle + the GPU's PCI bus id
 }
 
-// Hyperparameters.cs:80-121 names and defaults (wk_config_defaults) + the batched extensions
+// wk_config up to MaxGradNorm, its first 128 bytes: Hyperparameters.cs:80-121 names and defaults + the batched extensions.
+// The library reads and writes the whole wk_config, WkConfigLogStd below, which every import takes.
 [StructLayout(LayoutKind.Sequential)]
 public struct WkConfig
 {
@@ -47,6 +48,29 @@ public struct WkConfig
     // MaxGradNorm: 0 = off, above 0 = every Adam step scales the critic's and the actor's summed gradient down to that L2 norm
     // (float.PositiveInfinity measures only, wk_grad_norms_get returns the record, the IPC exchange refuses such a context)
     public float MaxGradNorm;
+}
+
+// wk_config as include/wk_api.h declares it (wk_config_defaults fills it): WkConfig's fields in WkConfig's order,
+// then the five of the trained log-std
+[StructLayout(LayoutKind.Sequential)]
+public struct WkConfigLogStd
+{
+    public int GameSpeed, Iterations, MaxTimesteps, RoughFloor, Epochs, BatchSize, UseGAE,
+               NormalizeAdvantages;
+    public float Gamma, Lambda, Epsilon, LogStandardDeviation, Alpha, Beta1, Beta2, AdamEpsilon;
+    public IntPtr CriticNeuralNetwork, ActorNeuralNetwork;  // NULL = the default networks
+    public float DeltaTime;
+    public int Horizon, Minibatch, MinibatchGlobal, EnvOffset, RandomizeStart, RandomizeMaterial;
+    public int LanesPerWalker, NetworkKernels, ReturnsMode;
+    public float TargetKL;
+    public float MaxGradNorm;
+    // LearnLogStd: 0 = the log-std is the constant LogStandardDeviation (or what wk_set_log_std set), 1 = after every epoch of
+    // wk_ppo_update one pass over the trajectory buffer forms the clipped surrogate's derivative by the scalar log-std and the host
+    // takes one Adam step on it (one stream synchronise per epoch, one GPU: the wk_comm_* initialisers refuse such a context)
+    public int LearnLogStd;
+    // LogStdAlpha: that step's learning rate (0 = the context's Alpha).  EntropyCoef: the entropy bonus's weight (needs LearnLogStd = 1).
+    // LogStdMin / LogStdMax: the clamp after every step, -5 < LogStdMin <= LogStandardDeviation <= LogStdMax < 5
+    public float LogStdAlpha, EntropyCoef, LogStdMin, LogStdMax;
 }
 
 // SerializableHyperparameters' host-only fields (Hyperparameters.cs:11-77)
@@ -149,6 +173,24 @@ public unsafe struct WkGradNorms
     public fixed int Pad[2];
 }
 
+// wk_log_std_gradient: the clipped surrogate's derivative by the scalar log-std over the trajectory buffer, host-divided
+[StructLayout(LayoutKind.Sequential)]
+public struct WkLogStdGrad
+{
+    public long Samples, Skipped;
+    public double GradSurrogate, Grad, Z2Mean;
+}
+
+// wk_get_log_std: the policy's log-std, the Adam state of the scalar and the last update's counters
+[StructLayout(LayoutKind.Sequential)]
+public struct WkLogStdState
+{
+    public float LogStd, Std;
+    public int T, Pad;
+    public double M, V, Entropy, GradLast;
+    public long Steps, Clamped, Nonfinite;
+}
+
 // wk_evaluate: complete episodes under the current actor on a private copy of the walkers
 [StructLayout(LayoutKind.Sequential)]
 public struct WkEvalArgs
@@ -207,9 +249,9 @@ public static class Wk
 {
     const string Lib = "wk";  // libwk.so next to the executable (or on LD_LIBRARY_PATH)
 
-    [DllImport(Lib)] public static extern void wk_config_defaults(ref WkConfig cfg);
+    [DllImport(Lib)] public static extern void wk_config_defaults(ref WkConfigLogStd cfg);
     [DllImport(Lib)] public static extern IntPtr wk_version();
-    [DllImport(Lib)] public static extern int wk_create(ref WkConfig cfg, int device, int nEnv, ulong seed, out IntPtr ctx);
+    [DllImport(Lib)] public static extern int wk_create(ref WkConfigLogStd cfg, int device, int nEnv, ulong seed, out IntPtr ctx);
     [DllImport(Lib)] public static extern int wk_destroy(IntPtr ctx);
     [DllImport(Lib)] public static extern IntPtr wk_last_error(IntPtr ctx);
     [DllImport(Lib)] public static extern int wk_sync(IntPtr ctx);
@@ -241,10 +283,10 @@ public static class Wk
     [DllImport(Lib)] public static extern int wk_get_adam(IntPtr ctx, float[]? m, float[]? v, out int t);
     [DllImport(Lib)] public static extern int wk_set_adam(IntPtr ctx, float[]? m, float[]? v, int t);
     [DllImport(Lib)] public static extern void wk_host_settings_defaults(ref WkHostSettings host);
-    [DllImport(Lib)] public static extern int wk_config_to_json(ref WkConfig cfg, ref WkHostSettings host, byte[] text, UIntPtr cap);
-    [DllImport(Lib, CharSet = CharSet.Ansi)] public static extern int wk_config_from_json(string json, ref WkConfig cfg, ref WkHostSettings host);
-    [DllImport(Lib, CharSet = CharSet.Ansi)] public static extern int wk_config_save_json(string path, ref WkConfig cfg, ref WkHostSettings host);
-    [DllImport(Lib, CharSet = CharSet.Ansi)] public static extern int wk_config_load_json(string path, ref WkConfig cfg, ref WkHostSettings host);
+    [DllImport(Lib)] public static extern int wk_config_to_json(ref WkConfigLogStd cfg, ref WkHostSettings host, byte[] text, UIntPtr cap);
+    [DllImport(Lib, CharSet = CharSet.Ansi)] public static extern int wk_config_from_json(string json, ref WkConfigLogStd cfg, ref WkHostSettings host);
+    [DllImport(Lib, CharSet = CharSet.Ansi)] public static extern int wk_config_save_json(string path, ref WkConfigLogStd cfg, ref WkHostSettings host);
+    [DllImport(Lib, CharSet = CharSet.Ansi)] public static extern int wk_config_load_json(string path, ref WkConfigLogStd cfg, ref WkHostSettings host);
     [DllImport(Lib, CharSet = CharSet.Ansi)] public static extern int wk_save_weights(IntPtr ctx, string criticPath, string actorPath);
     [DllImport(Lib, CharSet = CharSet.Ansi)] public static extern int wk_load_weights(IntPtr ctx, string criticPath, string actorPath);
     [DllImport(Lib)] public static extern int wk_format_weights(float[] p, byte[] critic, UIntPtr criticCap, byte[] actor, UIntPtr actorCap);
@@ -275,6 +317,10 @@ public static class Wk
     [DllImport(Lib)] public static extern int wk_grad_norms_get(IntPtr ctx, out WkGradNorms norms);
     [DllImport(Lib)] public static extern int wk_set_learning_rate(IntPtr ctx, float alpha);
     [DllImport(Lib)] public static extern int wk_get_learning_rate(IntPtr ctx, out float alpha);
+    [DllImport(Lib)] public static extern int wk_get_log_std(IntPtr ctx, out WkLogStdState state);
+    [DllImport(Lib)] public static extern int wk_set_log_std(IntPtr ctx, float logStd);
+    [DllImport(Lib)] public static extern int wk_set_log_std_adam(IntPtr ctx, double m, double v, int t);
+    [DllImport(Lib)] public static extern int wk_log_std_gradient(IntPtr ctx, out WkLogStdGrad grad);
     [DllImport(Lib)] public static extern int wk_evaluate(IntPtr ctx, ref WkEvalArgs args, out WkEvalStats stats, [Out] WkEvalRec[]? recs);
     [DllImport(Lib)] public static extern int wk_evaluate_time(IntPtr ctx, int reps, out double stepMs, out double foldMs);
     [DllImport(Lib)] public static extern int wk_train_batch(IntPtr ctx, int B, float bDiv, float[] states, float[] actions, float[] logpOld, float[] returns, float[] adv, out float criticDiag, out float actorDiag, float[]? gradsOut, int applyAdam, out int skipped);

@@ -121,7 +121,9 @@ namespace PPO {
 // c.TargetKL > 0 ends an update's epochs once the approximate KL to the collecting policy passes
 // it (PPOAgent::UpdateStatistics returns the last check).
 // c.MaxGradNorm > 0 scales the critic's and the actor's gradient down to that L2 norm in every
-// Adam step (PPOAgent::GradNorms returns the update's record)
+// Adam step (PPOAgent::GradNorms returns the update's record).
+// c.LearnLogStd = 1 trains the policy's log-std after every epoch, with c.EntropyCoef as the
+// entropy bonus's weight (PPOAgent::LogStd returns its state)
 struct Hyperparameters {
   wk_config c;
   Hyperparameters() { wk_config_defaults(&c); }
@@ -214,6 +216,28 @@ class PPOAgent {
     float a = 0.0f;
     if (wk_get_learning_rate(ctx_, &a) != WK_OK) LogError(wk_last_error(ctx_));
     return a;
+  }
+  // The policy's scalar log-std (c.LearnLogStd = 1 trains it after every epoch of Train; a host
+  // may also anneal it itself on any context) and the pass that forms its gradient.  Zeroed
+  // records on failure
+  wk_log_std_state LogStd() {
+    wk_log_std_state s{};
+    if (wk_get_log_std(ctx_, &s) != WK_OK) LogError(wk_last_error(ctx_));
+    return s;
+  }
+  void SetLogStd(float logStd) {
+    if (wk_set_log_std(ctx_, logStd) != WK_OK)
+      LogError(std::string("Exception while setting the log standard deviation: ") + wk_last_error(ctx_));
+  }
+  void SetLogStdAdam(double m, double v, int t) {
+    if (wk_set_log_std_adam(ctx_, m, v, t) != WK_OK)
+      LogError(std::string("Exception while setting the log standard deviation's Adam state: ") + wk_last_error(ctx_));
+  }
+  wk_log_std_grad LogStdGradient() {
+    wk_log_std_grad g{};
+    if (wk_log_std_gradient(ctx_, &g) != WK_OK)
+      LogError(std::string("Exception while reading the log standard deviation's gradient: ") + wk_last_error(ctx_));
+    return g;
   }
   // How good the policy is now (the counterpart of the console's _bestDistance and last-episode
   // average reward, Environment.cs:55-60,119): every walker plays complete episodes under the

@@ -78,6 +78,11 @@ struct wk_ctx {
   // the steps launched since it was last cleared
   wk::GradNormRec* gnorm = nullptr;
   int64_t gnorm_steps = 0;
+  // LearnLogStd = 1: the host's Adam step on the scalar log-std (P.log_std holds the value itself
+  // on every context) and the counters of the last wk_ppo_update (wk_get_log_std)
+  double ls_m = 0.0, ls_v = 0.0, ls_grad_last = 0.0;
+  int ls_t = 0;
+  int64_t ls_steps = 0, ls_clamped = 0, ls_nonfinite = 0;
   // data collection (ConsoleRenderer.AddTotalEpisodeReward / AddCriticLoss / AddActorLoss)
   int collect = 1;
   uint32_t rollout_steps = 0;  // env-steps taken by wk_rollout so far (episode log clock)
@@ -116,6 +121,8 @@ struct wk_ctx {
   // wk_snapshot: one device block holding every snapshotted buffer, plus the host counters
   void* snap = nullptr; size_t snap_bytes = 0;
   int snap_adam_t = 0; uint32_t snap_rollout_steps = 0; uint64_t snap_loss_count = 0;
+  float snap_log_std = 0.0f; double snap_ls_m = 0.0, snap_ls_v = 0.0; int snap_ls_t = 0;  // LearnLogStd = 1
+  double snap_ls_grad_last = 0.0; int64_t snap_ls_cnt[3] = {0, 0, 0};  // (what wk_get_log_std reports)
   bool snap_valid = false;
   bool snap_log_drained = false;  // wk_episode_log_drain since the save: the saved count's records are gone
   unsigned long long* counts = nullptr;  // [WK_NEV] device (wk_count_events)
@@ -306,6 +313,11 @@ void wk_config_defaults(wk_config* c) {
   c->ReturnsMode = 0;
   c->TargetKL = 0.0f;
   c->MaxGradNorm = 0.0f;
+  c->LearnLogStd = 0;
+  c->LogStdAlpha = 0.0f;
+  c->EntropyCoef = 0.0f;
+  c->LogStdMin = -4.0f;
+  c->LogStdMax = 1.0f;
 }
 
 const char* wk_version(void) { return "wk 0.1 (gfx950)"; }
@@ -355,6 +367,18 @@ static int validate(const wk_config* c, std::string& why) {
     return bad("TargetKL must be finite and >= 0 (0: no early stop)");
   if (!(c->MaxGradNorm >= 0.0f))  // (a NaN compares false; +inf measures only)
     return bad("MaxGradNorm must be >= 0 and not NaN (0: no clipping, inf: measure only)");
+  if (c->LearnLogStd != 0 && c->LearnLogStd != 1)
+    return bad("LearnLogStd must be 0 (a constant log-std) or 1 (trained after every epoch)");
+  if (!std::isfinite(c->LogStdAlpha) || c->LogStdAlpha < 0.0f)
+    return bad("LogStdAlpha must be finite and >= 0 (0: the context's Alpha)");
+  if (!std::isfinite(c->EntropyCoef) || c->EntropyCoef < 0.0f)
+    return bad("EntropyCoef must be finite and >= 0");
+  if (c->EntropyCoef > 0.0f && c->LearnLogStd == 0)
+    return bad("EntropyCoef > 0 needs LearnLogStd = 1: with a fixed log-std the entropy bonus is a constant");
+  if (c->LearnLogStd == 1 &&
+      !(c->LogStdMin > -5.0f && c->LogStdMin <= c->LogStandardDeviation &&
+        c->LogStandardDeviation <= c->LogStdMax && c->LogStdMax < 5.0f))  // (a NaN compares false)
+    return bad("LearnLogStd = 1 needs -5 < LogStdMin <= LogStandardDeviation <= LogStdMax < 5");
   if (c->Horizon <= 0) return bad("Horizon must be > 0");
   if (c->Minibatch < 0) return bad("Minibatch must be >= 0");
   if (c->LanesPerWalker != 0 && c->LanesPerWalker != 1 && c->LanesPerWalker != 2 &&
@@ -394,6 +418,15 @@ static std::array<TrajRow, 8> traj_rows(wk_ctx* c) {
   return {{{"ts", (void**)&c->ts, 12 * f}, {"ta", (void**)&c->ta, 4 * f}, {"tlp", (void**)&c->tlp, 4 * f},
            {"tr", (void**)&c->tr, f}, {"td", (void**)&c->td, 1}, {"tv", (void**)&c->tv, f},
            {"tret", (void**)&c->tret, f}, {"tadv", (void**)&c->tadv, f}}};
+}
+
+// The policy's log-std and everything derived from it, in one place (wk_create, wk_set_log_std,
+// the LearnLogStd step, snapshot and checkpoint): every kernel takes these by value at launch
+static void apply_log_std(wk_ctx* c, float log_std) {
+  c->P.log_std = log_std;
+  c->P.std_ = expf(log_std);
+  const float PI_F = 3.14159265358979323846f;
+  c->lp_const = -logf(c->P.std_) - logf(sqrtf(2.0f * PI_F));
 }
 
 int wk_create(const wk_config* cfg, int device, int n_env, uint64_t seed, wk_ctx** out) {
@@ -460,8 +493,7 @@ int wk_create(const wk_config* cfg, int device, int n_env, uint64_t seed, wk_ctx
   P.max_timesteps = c.MaxTimesteps;
   P.dt_frame = c.DeltaTime;
   P.dt_sub = c.DeltaTime / (float)c.Iterations;
-  P.log_std = c.LogStandardDeviation;
-  P.std_ = expf(c.LogStandardDeviation);
+  apply_log_std(x, c.LogStandardDeviation);
   P.seed = seed;
   P.env_offset = c.EnvOffset;
   // auto on the flat floor: the side-split pair mapping from 16,385 walkers up, the quad
@@ -486,8 +518,6 @@ int wk_create(const wk_config* cfg, int device, int n_env, uint64_t seed, wk_ctx
       while (wpw > 1 && (size_t)n_env <= (size_t)512 * wpw) wpw >>= 1;  // n / (wpw / 2) <= 1,024 waves
     P.wpw = wpw;
   }
-  const float PI_F = 3.14159265358979323846f;
-  x->lp_const = -logf(P.std_) - logf(sqrtf(2.0f * PI_F));
 
   const size_t n = (size_t)n_env, T = (size_t)x->T;
 #define ALLOC(ptr, bytes)                                                   \
@@ -1633,9 +1663,9 @@ static wk::GradArgs traj_grad_args(wk_ctx* c, int M, float b_div) {
 static int stats_blocks_for(wk_ctx* c, int rows) {
   return c->general ? wk::net_stats_blocks(rows) : wk::ppo_stats_blocks(rows);
 }
-static hipError_t launch_stats_for(wk_ctx* c, const wk::StatsArgs& a, int nblocks) {
-  return c->general ? wk::launch_net_stats(a, c->net_dev, c->act_rows, c->stream)
-                    : wk::launch_ppo_stats(a, nblocks, c->stream);
+static hipError_t launch_stats_for(wk_ctx* c, const wk::StatsArgs& a, int nblocks, bool log_std) {
+  return c->general ? wk::launch_net_stats(a, c->net_dev, c->act_rows, log_std, c->stream)
+                    : wk::launch_ppo_stats(a, nblocks, log_std, c->stream);
 }
 
 // wk_ppo_stats from the device's record: the host divides
@@ -1664,7 +1694,10 @@ static void stats_from_rec(const wk::StatsRec& r, wk_ppo_stats* o) {
 // and the per-epoch check of a TargetKL > 0 update): forward kernel, k_stats_finish, the record
 // and the optional per-row outputs copied to the host.  Stale returns are computed first, and
 // whether they count as valid is left as it was.
-static int stats_impl(wk_ctx* c, wk_ppo_stats* out, float* logp_new, float* values_new) {
+// ls: the log-std pass instead (wk_log_std_gradient, the LearnLogStd step) -- the kernels' wide
+// instantiation, whose record holds the statistics' record too; out may then be null.
+static int stats_impl(wk_ctx* c, wk_ppo_stats* out, float* logp_new, float* values_new,
+                      wk_log_std_grad* ls = nullptr) {
   if (c->T_valid <= 0) { SETERR(c, "wk_policy_stats before wk_rollout / wk_set_trajectory"); return WK_ERR_STATE; }
   if (!c->returns_valid) {
     int r = returns_impl(c);
@@ -1679,23 +1712,110 @@ static int stats_impl(wk_ctx* c, wk_ppo_stats* out, float* logp_new, float* valu
   a.g.states = c->ts; a.g.actions = c->ta; a.g.logp_old = c->tlp; a.g.returns = c->tret; a.g.adv = c->tadv;
   a.g.pool = (uint32_t)rows;
   a.g.samples = (int)rows;
-  wk::StatsRec* d_rec;
+  const bool wide = ls != nullptr;
+  const size_t rec_bytes = wide ? sizeof(wk::StatsRecLS) : sizeof(wk::StatsRec);
+  void* d_rec;
   if (carve(c, &c->scratch2, &c->scratch2_bytes,
-            {{&a.partial, sizeof(wk::StatsRec) * (size_t)nblocks}, {&d_rec, sizeof(wk::StatsRec)},
+            {{&a.partial, rec_bytes * (size_t)nblocks}, {&d_rec, rec_bytes},
              {&a.logp_new, logp_new ? sizeof(float) * 4 * rows : 0},
              {&a.values_new, values_new ? sizeof(float) * rows : 0}}))
     return WK_ERR_HIP;
-  HIPCHK(c, launch_stats_for(c, a, nblocks));
-  HIPCHK(c, wk::launch_stats_finish(a.partial, nblocks, d_rec, c->stream));
-  wk::StatsRec rec;
-  HIPCHK(c, hipMemcpyAsync(&rec, d_rec, sizeof(rec), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, launch_stats_for(c, a, nblocks, wide));
+  HIPCHK(c, wk::launch_stats_finish(a.partial, nblocks, wide, d_rec, c->stream));
+  wk::StatsRecLS recw{};
+  wk::StatsRec& rec = recw.s;  // (the wide record starts with the statistics' record)
+  HIPCHK(c, hipMemcpyAsync(&recw, d_rec, rec_bytes, hipMemcpyDeviceToHost, c->stream));
   if (logp_new)
     HIPCHK(c, hipMemcpyAsync(logp_new, a.logp_new, sizeof(float) * 4 * rows, hipMemcpyDeviceToHost, c->stream));
   if (values_new)
     HIPCHK(c, hipMemcpyAsync(values_new, a.values_new, sizeof(float) * rows, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  stats_from_rec(rec, out);
+  if (out) stats_from_rec(rec, out);
+  if (ls) {  // the host divides (0 / 0: no counted row gives NaN)
+    const double ne = 4.0 * (double)rec.rows;
+    ls->samples = rec.rows;
+    ls->skipped = rec.skipped;
+    ls->grad_surrogate = -recw.term / ne;
+    ls->grad = ls->grad_surrogate - (double)c->cfg.EntropyCoef;
+    ls->z2_mean = recw.zz / ne;
+  }
   return WK_OK;
+}
+
+int wk_log_std_gradient(wk_ctx* c, wk_log_std_grad* out) {
+  DevGuard dg_(c);
+  if (!c || !out) return WK_ERR_ARG;
+  return stats_impl(c, nullptr, nullptr, nullptr, out);
+}
+
+int wk_get_log_std(wk_ctx* c, wk_log_std_state* out) {
+  if (!c || !out) return WK_ERR_ARG;
+  memset(out, 0, sizeof(*out));
+  out->log_std = c->P.log_std;
+  out->std = c->P.std_;
+  out->entropy = (double)c->P.log_std + 0.5 * std::log(2.0 * 3.14159265358979323846 * 2.71828182845904523536);
+  if (c->cfg.LearnLogStd != 1) return WK_OK;
+  out->t = c->ls_t;
+  out->m = c->ls_m;
+  out->v = c->ls_v;
+  out->grad_last = c->ls_grad_last;
+  out->steps = c->ls_steps;
+  out->clamped = c->ls_clamped;
+  out->nonfinite = c->ls_nonfinite;
+  return WK_OK;
+}
+
+int wk_set_log_std(wk_ctx* c, float log_std) {
+  if (!c) return WK_ERR_ARG;
+  if (!std::isfinite(log_std) || log_std <= -5.0f || log_std >= 5.0f) {
+    SETERR(c, "wk_set_log_std: the log-std must be finite and inside (-5, 5)");
+    return WK_ERR_ARG;
+  }
+  if (c->cfg.LearnLogStd == 1 && (log_std < c->cfg.LogStdMin || log_std > c->cfg.LogStdMax)) {
+    SETERR(c, "wk_set_log_std: %g is outside [LogStdMin, LogStdMax] = [%g, %g]", (double)log_std,
+           (double)c->cfg.LogStdMin, (double)c->cfg.LogStdMax);
+    return WK_ERR_ARG;
+  }
+  apply_log_std(c, log_std);
+  return WK_OK;
+}
+
+int wk_set_log_std_adam(wk_ctx* c, double m, double v, int t) {
+  if (!c) return WK_ERR_ARG;
+  if (c->cfg.LearnLogStd != 1) {
+    SETERR(c, "wk_set_log_std_adam: the context does not train its log-std (LearnLogStd = 0)");
+    return WK_ERR_STATE;
+  }
+  if (!std::isfinite(m) || !std::isfinite(v) || v < 0.0 || t < 0) {
+    SETERR(c, "wk_set_log_std_adam: m and v must be finite, v and t not negative");
+    return WK_ERR_ARG;
+  }
+  c->ls_m = m;
+  c->ls_v = v;
+  c->ls_t = t;
+  return WK_OK;
+}
+
+// One Adam step on the scalar log-std, on the host in double, from the pass's record; a
+// non-finite gradient (or no counted row: 0 / 0) takes no step and is counted
+static void log_std_step(wk_ctx* c, const wk_log_std_grad& g) {
+  c->ls_grad_last = g.grad;
+  if (!std::isfinite(g.grad)) {
+    c->ls_nonfinite++;
+    return;
+  }
+  const double b1 = (double)c->cfg.Beta1, b2 = (double)c->cfg.Beta2, eps = (double)c->cfg.AdamEpsilon;
+  const double lr = c->cfg.LogStdAlpha > 0.0f ? (double)c->cfg.LogStdAlpha : (double)c->cfg.Alpha;
+  c->ls_m = b1 * c->ls_m + (1.0 - b1) * g.grad;
+  c->ls_v = b2 * c->ls_v + (1.0 - b2) * g.grad * g.grad;
+  c->ls_t += 1;
+  const double mh = c->ls_m / (1.0 - std::pow(b1, (double)c->ls_t));
+  const double vh = c->ls_v / (1.0 - std::pow(b2, (double)c->ls_t));
+  const float s = (float)((double)c->P.log_std - lr * mh / (std::sqrt(vh) + eps));
+  const float sc = std::min(std::max(s, c->cfg.LogStdMin), c->cfg.LogStdMax);
+  if (sc != s) c->ls_clamped++;
+  c->ls_steps++;
+  apply_log_std(c, sc);
 }
 
 int wk_policy_stats(wk_ctx* c, wk_ppo_stats* out, float* logp_new, float* values_new) {
@@ -2008,6 +2128,7 @@ int wk_ppo_update(wk_ctx* c, const wk_ppo_args* args, float* critic_diag, float*
 
 static int ppo_update_impl(wk_ctx* c, const wk_ppo_args* args) {
   c->upd_stats_valid = false;
+  c->ls_steps = c->ls_clamped = c->ls_nonfinite = 0;
   if (!c->returns_valid) {
     int r = returns_impl(c);
     if (r) return r;
@@ -2032,8 +2153,20 @@ static int ppo_update_impl(wk_ctx* c, const wk_ppo_args* args) {
     }
     // TargetKL: the policy's distance from the one that collected the data, after every epoch
     // (the last included); past the target the remaining epochs are not run (a NaN never stops)
+    // LearnLogStd: the same pass, widened, yields the log-std's gradient as well (one pass per
+    // epoch, not two); the step on the scalar comes before the stop decision, and g takes the new
+    // std for the next epoch's gradient kernels
+    const bool learn = c->cfg.LearnLogStd == 1;
+    if (learn) {
+      wk_log_std_grad lg;
+      if (int r = stats_impl(c, c->cfg.TargetKL > 0.0f ? &c->upd_stats : nullptr, nullptr, nullptr, &lg)) return r;
+      log_std_step(c, lg);
+      g.std_ = c->P.std_;
+      g.lp_const = c->lp_const;
+    }
     if (c->cfg.TargetKL > 0.0f) {
-      if (int r = stats_impl(c, &c->upd_stats, nullptr, nullptr)) return r;
+      if (!learn)
+        if (int r = stats_impl(c, &c->upd_stats, nullptr, nullptr)) return r;
       const bool stop = c->upd_stats.kl > (double)c->cfg.TargetKL;
       c->upd_stats.epochs_run = e + 1;
       c->upd_stats.stopped_early = (stop && e + 1 < epochs) ? 1 : 0;
@@ -2103,6 +2236,12 @@ static int refuse_comm(wk_ctx* c) {
   if (c->cfg.TargetKL > 0.0f) {
     SETERR(c, "the multi-GPU gradient exchange refuses a TargetKL > 0 context: every rank would "
               "decide on its own shard's statistics");
+    return WK_ERR_CONFIG;
+  }
+  // ranks stepping the log-std on their own shards' gradients would diverge
+  if (c->cfg.LearnLogStd == 1) {
+    SETERR(c, "the multi-GPU gradient exchange refuses a LearnLogStd = 1 context: every rank would "
+              "step the log-std on its own shard's gradient");
     return WK_ERR_CONFIG;
   }
   if (!c->general) return WK_OK;
@@ -2364,6 +2503,10 @@ int wk_snapshot(wk_ctx* c, int op) {
   if (op == 0) {
     if (ensure(c, &c->snap, &c->snap_bytes, total)) return WK_ERR_HIP;
     c->snap_adam_t = c->adam_t;
+    c->snap_log_std = c->P.log_std;
+    c->snap_ls_m = c->ls_m; c->snap_ls_v = c->ls_v; c->snap_ls_t = c->ls_t;
+    c->snap_ls_grad_last = c->ls_grad_last;
+    c->snap_ls_cnt[0] = c->ls_steps; c->snap_ls_cnt[1] = c->ls_clamped; c->snap_ls_cnt[2] = c->ls_nonfinite;
     c->snap_rollout_steps = c->rollout_steps;
     c->snap_loss_count = c->loss_count;
     c->snap_log_drained = false;
@@ -2382,6 +2525,14 @@ int wk_snapshot(wk_ctx* c, int op) {
     c->snap_valid = true;
   } else {
     c->adam_t = c->snap_adam_t;
+    // the trained log-std and its Adam state are part of the model; on a LearnLogStd = 0 context
+    // the log-std is configuration (wk_set_log_std), like the learning rate, and stays
+    if (c->cfg.LearnLogStd == 1) {
+      apply_log_std(c, c->snap_log_std);
+      c->ls_m = c->snap_ls_m; c->ls_v = c->snap_ls_v; c->ls_t = c->snap_ls_t;
+      c->ls_grad_last = c->snap_ls_grad_last;
+      c->ls_steps = c->snap_ls_cnt[0]; c->ls_clamped = c->snap_ls_cnt[1]; c->ls_nonfinite = c->snap_ls_cnt[2];
+    }
     c->rollout_steps = c->snap_rollout_steps;
     c->loss_count = c->snap_loss_count;
     // the records the saved count stood for were handed out by a drain since, and rollouts have
@@ -2546,6 +2697,18 @@ const uint32_t kCkptVersion = 4;
 // uint32 lengths and the critic and actor strings, and nparam parameters of that network.  A
 // built-in context still writes version 4, byte for byte as before
 const uint32_t kCkptVersionNet = 5;
+// 6: a LearnLogStd = 1 context of either kernel family (CkptExt.reserved1 = 1; reserved0 still
+// tells the family): after the version-5 network section, if any, the trained log-std and its
+// Adam state.  A LearnLogStd = 0 context still writes version 4 or 5, byte for byte as before
+const uint32_t kCkptVersionLogStd = 6;
+#pragma pack(push, 4)
+struct CkptLogStd {
+  float log_std;
+  int32_t t;
+  double m, v;
+};
+#pragma pack(pop)
+static_assert(sizeof(CkptLogStd) == 24, "checkpoint log-std section");
 // The file's fixed sections, in file order, between its variable head (header, CkptExt, the
 // version-5 network section) and its scene section: the only place that knows the order
 std::array<Seg, 9> ckpt_sections(const wk_ctx* c) {
@@ -2664,13 +2827,19 @@ int wk_checkpoint_save(wk_ctx* c, const char* path) {
   DevGuard dg_(c);
   if (!c || !path) return WK_ERR_ARG;
   const size_t n = c->n;
-  CkptHeader h{kCkptMagic, c->general ? kCkptVersionNet : kCkptVersion, (uint32_t)n, (uint32_t)wk::NSTATE,
+  const bool learn = c->cfg.LearnLogStd == 1;
+  CkptHeader h{kCkptMagic, learn ? kCkptVersionLogStd : (c->general ? kCkptVersionNet : kCkptVersion),
+               (uint32_t)n, (uint32_t)wk::NSTATE,
                (uint32_t)c->np, (uint32_t)c->adam_t, c->seed, c->cfg.EnvOffset, c->cfg.Iterations,
                c->cfg.MaxTimesteps, c->rollout_steps};
   const int np = c->scene.n_props;
   const size_t scene_bytes = sizeof(int32_t) + sizeof(wk_prop) * np + sizeof(float) * n * c->scene.pstride;
-  const CkptExt ext{c->cfg.RoughFloor, c->P.lanes, c->general ? 1 : 0, 0};
-  const std::string nets = c->general ? net_section(c) : std::string();
+  const CkptExt ext{c->cfg.RoughFloor, c->P.lanes, c->general ? 1 : 0, learn ? 1 : 0};
+  std::string nets = c->general ? net_section(c) : std::string();
+  if (learn) {  // (the variable head: network section, then the log-std section)
+    const CkptLogStd ls{c->P.log_std, c->ls_t, c->ls_m, c->ls_v};
+    nets.append((const char*)&ls, sizeof ls);
+  }
   std::vector<char> buf(sizeof h + sizeof ext + nets.size() + ckpt_offset(c, nullptr) + scene_bytes);
   char* q = buf.data();
   memcpy(q, &h, sizeof h); q += sizeof h;
@@ -2703,7 +2872,7 @@ int wk_checkpoint_load(wk_ctx* c, const char* path) {
   CkptHeader h;
   if (data.size() < sizeof h) { SETERR(c, "checkpoint '%s' truncated", path); return WK_ERR_ARG; }
   memcpy(&h, data.data(), sizeof h);
-  if (h.magic != kCkptMagic || h.version < 2 || h.version > kCkptVersionNet) {
+  if (h.magic != kCkptMagic || h.version < 2 || h.version > kCkptVersionLogStd) {
     SETERR(c, "'%s' is not a wk checkpoint", path);
     return WK_ERR_ARG;
   }
@@ -2721,7 +2890,13 @@ int wk_checkpoint_load(wk_ctx* c, const char* path) {
   if (data.size() >= sizeof h + ext_bytes) memcpy(&ext, data.data() + sizeof h, sizeof ext);
   // the networks first: a file of other networks (or of the other kind of kernels) has another
   // parameter count and layout
-  const bool file_general = h.version >= kCkptVersionNet;
+  const bool file_learn = h.version >= kCkptVersionLogStd;
+  const bool file_general = file_learn ? ext.reserved0 != 0 : h.version >= kCkptVersionNet;
+  if (file_learn != (c->cfg.LearnLogStd == 1) || (ext.reserved1 != 0) != file_learn) {
+    SETERR(c, "checkpoint '%s' was written with LearnLogStd %d (context: %d)", path, file_learn ? 1 : 0,
+           c->cfg.LearnLogStd);
+    return WK_ERR_ARG;
+  }
   if (file_general != c->general || (ext.reserved0 != 0) != c->general) {
     SETERR(c, "checkpoint '%s' was written with NetworkKernels %d (context: %d)", path,
            file_general ? 1 : 0, c->general ? 1 : 0);
@@ -2736,6 +2911,18 @@ int wk_checkpoint_load(wk_ctx* c, const char* path) {
       return WK_ERR_ARG;
     }
     ext_bytes += mine.size();
+  }
+  CkptLogStd ls{};
+  if (file_learn) {  // its value is checked like wk_set_log_std's and wk_set_log_std_adam's
+    if (data.size() < sizeof h + ext_bytes + sizeof ls) { SETERR(c, "checkpoint '%s' truncated", path); return WK_ERR_ARG; }
+    memcpy(&ls, data.data() + sizeof h + ext_bytes, sizeof ls);
+    if (!std::isfinite(ls.log_std) || ls.log_std < c->cfg.LogStdMin || ls.log_std > c->cfg.LogStdMax ||
+        !std::isfinite(ls.m) || !std::isfinite(ls.v) || ls.v < 0.0 || ls.t < 0) {
+      SETERR(c, "checkpoint '%s': invalid log-std section (log_std %g outside [%g, %g], or its Adam state)",
+             path, (double)ls.log_std, (double)c->cfg.LogStdMin, (double)c->cfg.LogStdMax);
+      return WK_ERR_ARG;
+    }
+    ext_bytes += sizeof ls;
   }
   size_t need = sizeof h + ext_bytes + ckpt_offset(c, nullptr) + sizeof(int32_t);
   int32_t np = 0;
@@ -2802,6 +2989,10 @@ int wk_checkpoint_load(wk_ctx* c, const char* path) {
     HIPCHK(c, hipMemcpy(c->props, q, sizeof(float) * n * c->scene.pstride, hipMemcpyHostToDevice));
   }
   c->adam_t = (int)h.adam_t;
+  if (file_learn) {
+    apply_log_std(c, ls.log_std);
+    c->ls_m = ls.m; c->ls_v = ls.v; c->ls_t = ls.t;
+  }
   c->rollout_steps = h.rollout_steps;
   c->T_valid = 0;
   c->returns_valid = 0;

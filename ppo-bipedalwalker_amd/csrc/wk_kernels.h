@@ -244,6 +244,17 @@ struct StatsRec {
 };
 enum : int { STATS_FIELDS = 11, STATS_COUNTS = 3, STATS_RMAX = 10 };
 static_assert(sizeof(StatsRec) == 8 * STATS_FIELDS, "StatsRec is STATS_FIELDS 64-bit words");
+// The log-std pass (wk_log_std_gradient, a LearnLogStd = 1 update): the <true> instantiation of
+// the same passes (kernels k_ppo_logstd and k_net_logstd) carries two trailing sums in double over
+// the counted entries -- the clipped surrogate's derivative by lp times d lp / d log_std = zz - 1,
+// and zz = ((act - mean) / std)^2.  StatsRec and STATS_FIELDS are the <false> instantiation's
+// (k_ppo_stats, k_net_stats), as before.
+struct StatsRecLS {
+  StatsRec s;
+  double term, zz;
+};
+enum : int { STATS_FIELDS_LS = STATS_FIELDS + 2 };
+static_assert(sizeof(StatsRecLS) == 8 * STATS_FIELDS_LS, "StatsRecLS is STATS_FIELDS_LS 64-bit words");
 // the built-in kernel's grid: at most STATS_MAX_BLOCKS blocks of STATS_WAVES waves, every wave
 // striding over the 16-row chunks (one grid pass = STATS_MAX_BLOCKS * STATS_WAVES * 16 rows)
 enum : int { STATS_MAX_BLOCKS = 512, STATS_WAVES = 4 };
@@ -251,13 +262,15 @@ struct StatsArgs {
   GradArgs g;               // the rows in buffer order: samples = rows, base 0, no permutation
   float* logp_new;          // [rows][4] or null
   float* values_new;        // [rows] or null
-  unsigned long long* partial;  // [blocks][STATS_FIELDS]
+  unsigned long long* partial;  // [blocks][STATS_FIELDS], log_std: [blocks][STATS_FIELDS_LS]
 };
+// log_std: the <true> instantiation and its record width, in all three launches
 int ppo_stats_blocks(int rows);
-hipError_t launch_ppo_stats(const StatsArgs& a, int nblocks, hipStream_t s);
+hipError_t launch_ppo_stats(const StatsArgs& a, int nblocks, bool log_std, hipStream_t s);
 int net_stats_blocks(int rows);
-hipError_t launch_net_stats(const StatsArgs& a, const NetDesc* nets, int act_rows, hipStream_t s);
-hipError_t launch_stats_finish(const unsigned long long* partial, int nblocks, StatsRec* out,
+hipError_t launch_net_stats(const StatsArgs& a, const NetDesc* nets, int act_rows, bool log_std,
+                            hipStream_t s);
+hipError_t launch_stats_finish(const unsigned long long* partial, int nblocks, bool log_std, void* out,
                                hipStream_t s);
 
 // Policy evaluation (wk_evaluate; wk_eval.hip).  The accounting kernel k_eval_step runs after

@@ -258,9 +258,12 @@ __global__ __launch_bounds__(64) void k_net_policy(EnvParams P, const NetDesc* _
 // Block b owns the consecutive tiles [b tpb, (b + 1) tpb), as in k_net_grad, and writes one
 // record; k_stats_finish (wk_stats.hip) sums the records in block order.  Every row is evaluated,
 // the skipped ones too (their log-densities and values are outputs); a row's column of the
-// activation image never meets another row's.
-__global__ __launch_bounds__(64) void k_net_stats(StatsArgs sa, const NetDesc* __restrict__ nets,
-                                                  int act_rows, int tiles_per_block) {
+// activation image never meets another row's.  LSTD: the log-std pass (wk_stats.h's LS; here
+// LS is the image's stride), same tiles; its two instantiations are the kernels k_net_stats
+// (<false>, as it always was) and k_net_logstd (<true>) below.
+template <bool LSTD>
+__device__ __forceinline__ void net_stats_pass(const StatsArgs& sa, const NetDesc* __restrict__ nets,
+                                               int act_rows, int tiles_per_block) {
   using namespace nt;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const GradArgs& ga = sa.g;
@@ -271,7 +274,7 @@ __global__ __launch_bounds__(64) void k_net_stats(StatsArgs sa, const NetDesc* _
   const int ntiles = (ga.samples + NS - 1) / NS;
   const int t0 = blockIdx.x * tiles_per_block;
   const int t1 = min(t0 + tiles_per_block, ntiles);
-  StatsAcc acc;
+  StatsAcc<LSTD> acc;
 #pragma unroll 1
   for (int tile = t0; tile < t1; tile++) {
     const int pos = tile * NS + s;
@@ -295,9 +298,19 @@ __global__ __launch_bounds__(64) void k_net_stats(StatsArgs sa, const NetDesc* _
     __syncthreads();  // the next tile rewrites the image
   }
   unsigned long long* rec = (unsigned long long*)(lds + ((act_rows * LS + 1) & ~1));
+  constexpr int NF = stats_fields<LSTD>();
   stats_put(acc, rec, lane);
   __syncthreads();
-  stats_block_fold<1>(rec, lane, sa.partial + (size_t)blockIdx.x * STATS_FIELDS);
+  stats_block_fold<1, NF>(rec, lane, sa.partial + (size_t)blockIdx.x * NF);
+}
+
+__global__ __launch_bounds__(64) void k_net_stats(StatsArgs sa, const NetDesc* __restrict__ nets,
+                                                  int act_rows, int tiles_per_block) {
+  net_stats_pass<false>(sa, nets, act_rows, tiles_per_block);
+}
+__global__ __launch_bounds__(64) void k_net_logstd(StatsArgs sa, const NetDesc* __restrict__ nets,
+                                                   int act_rows, int tiles_per_block) {
+  net_stats_pass<true>(sa, nets, act_rows, tiles_per_block);
 }
 
 struct NetGradArgs {
@@ -469,7 +482,8 @@ __global__ void k_net_xavier(float* W, uint64_t seed, const NetDesc* __restrict_
 // ---- host side ----
 static size_t policy_lds(int act_rows) { return sizeof(float) * (size_t)act_rows * nt::LS; }
 static size_t stats_lds(int act_rows) {
-  return sizeof(float) * (size_t)((act_rows * nt::LS + 1) & ~1) + sizeof(unsigned long long) * STATS_FIELDS * 64;
+  // (the wide record's room for both instantiations: one size, one attribute)
+  return sizeof(float) * (size_t)((act_rows * nt::LS + 1) & ~1) + sizeof(unsigned long long) * STATS_FIELDS_LS * 64;
 }
 static size_t grad_lds(int act_rows) {
   return sizeof(float) * ((size_t)(act_rows + 2 * nt::GROWS) * nt::LS + nt::M_END);
@@ -484,6 +498,9 @@ hipError_t configure_net_kernels() {
                             (int)policy_lds(rows));
   if (e == hipSuccess)
     e = hipFuncSetAttribute((const void*)k_net_stats, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)stats_lds(rows));
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute((const void*)k_net_logstd, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)stats_lds(rows));
   return e;
 }
@@ -530,9 +547,12 @@ hipError_t launch_net_grad(const GradArgs& g, const NetDesc* nets, int act_rows,
 // the statistics pass: k_net_grad's assignment of tiles to blocks
 int net_stats_blocks(int rows) { return net_grad_blocks(rows); }
 
-hipError_t launch_net_stats(const StatsArgs& a, const NetDesc* nets, int act_rows, hipStream_t s) {
-  hipLaunchKernelGGL(k_net_stats, dim3(net_stats_blocks(a.g.samples)), dim3(64), stats_lds(act_rows), s, a,
-                     nets, act_rows, net_tiles_per_block(a.g.samples));
+hipError_t launch_net_stats(const StatsArgs& a, const NetDesc* nets, int act_rows, bool log_std,
+                            hipStream_t s) {
+  const dim3 grid(net_stats_blocks(a.g.samples));
+  const int tpb = net_tiles_per_block(a.g.samples);
+  hipLaunchKernelGGL(log_std ? k_net_logstd : k_net_stats, grid, dim3(64), stats_lds(act_rows), s, a, nets,
+                     act_rows, tpb);
   return hipGetLastError();
 }
 

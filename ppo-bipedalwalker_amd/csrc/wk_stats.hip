@@ -1,7 +1,8 @@
 // wk_stats.hip -- policy statistics over the trajectory for the built-in networks (gfx950):
 // k_ppo_stats, a forward-only pass of the current actor and critic over every row of the buffer
 // with the per-entry statistics of wk_stats.h behind it, and k_stats_finish, the ordered sum of
-// the blocks' records (both kernel families).
+// the blocks' records (both kernel families); and k_ppo_logstd, the same pass instantiated with
+// the log-std's derivative (wk_log_std_gradient, the LearnLogStd step).
 //
 // The forward pass is k_ppo_grad_mfma's forward half restated (wk_ppo_mfma.hip: the weight image
 // Wz staged into LDS once per block, one wave per chunk of 16 rows, layer 1 and 2 on
@@ -30,7 +31,7 @@ enum : int {
   SX = 256,  // [16][16]: 12 features, then the gradient kernel's bias column (unused here)
   LDS_FLOATS = mf::WEND + WAVES * SX
 };
-static_assert((size_t)LDS_FLOATS * 4 >= (size_t)WAVES * STATS_FIELDS * 64 * 8, "the fold's images fit");
+static_assert((size_t)LDS_FLOATS * 4 >= (size_t)WAVES * STATS_FIELDS_LS * 64 * 8, "the fold's images fit");
 static_assert(LDS_FLOATS * 4 <= 64 * 1024, "static LDS");
 }  // namespace st
 
@@ -47,8 +48,12 @@ DEV f4 st_mfma(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x
 // (two waves per SIMD: a full grid is two blocks per CU, and the second wave fills the first's
 // MFMA dependency waits; biases and output rows are read from LDS where they are used, so the
 // 256 registers hold)
-__global__ __launch_bounds__(64 * st::WAVES) __attribute__((amdgpu_waves_per_eu(2)))
-void k_ppo_stats(StatsArgs sa) {
+// LS: the log-std pass (wk_stats.h) -- the same forward, grid and chunk ownership; the entry's
+// extra arithmetic, two more double sums per lane and two more words in the block's record.
+// The two instantiations are the kernels k_ppo_stats (<false>, as it always was) and
+// k_ppo_logstd (<true>) below.
+template <bool LS>
+DEV void ppo_stats_pass(const StatsArgs& sa) {
   using namespace mf;
   using namespace st;
   __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
@@ -103,7 +108,7 @@ void k_ppo_stats(StatsArgs sa) {
       wa1[Mt][t] = lds[AW1F + (Mt * 3 + t) * 64 + lane];
       wc1[Mt][t] = lds[CW1F + (Mt * 3 + t) * 64 + lane];
     }
-  StatsAcc acc;
+  StatsAcc<LS> acc;
 #pragma unroll 1
   for (; c < nchunks; c += nw) {
     const Smp cur = nxt;
@@ -195,18 +200,24 @@ void k_ppo_stats(StatsArgs sa) {
 
   // ---- lanes in lane order, waves in wave order, one record per block ----
   __syncthreads();  // every wave is done with the weights and tiles
+  constexpr int NF = stats_fields<LS>();
   unsigned long long* rec = (unsigned long long*)lds;
-  stats_put(acc, rec + (size_t)wave * STATS_FIELDS * 64, lane);
+  stats_put(acc, rec + (size_t)wave * NF * 64, lane);
   __syncthreads();
-  stats_block_fold<WAVES>(rec, tid, sa.partial + (size_t)blockIdx.x * STATS_FIELDS);
+  stats_block_fold<WAVES, NF>(rec, tid, sa.partial + (size_t)blockIdx.x * NF);
 }
 
+__global__ __launch_bounds__(64 * st::WAVES) __attribute__((amdgpu_waves_per_eu(2)))
+void k_ppo_stats(StatsArgs sa) { ppo_stats_pass<false>(sa); }
+__global__ __launch_bounds__(64 * st::WAVES) __attribute__((amdgpu_waves_per_eu(2)))
+void k_ppo_logstd(StatsArgs sa) { ppo_stats_pass<true>(sa); }
+
 // the blocks' records in block order: sums, counts and the maximum, nothing else (the host
-// divides); one block, thread f owns field f
+// divides); one block, thread f owns field f of records `nfields` words wide
 __global__ __launch_bounds__(64) void k_stats_finish(const unsigned long long* __restrict__ partial,
-                                                     int nblocks, unsigned long long* out) {
+                                                     int nblocks, int nfields, unsigned long long* out) {
   const int f = threadIdx.x;
-  if (f < STATS_FIELDS) out[f] = stats_fold(partial + f, nblocks, STATS_FIELDS, f);
+  if (f < nfields) out[f] = stats_fold(partial + f, nblocks, nfields, f);
 }
 
 int ppo_stats_blocks(int rows) {
@@ -215,14 +226,15 @@ int ppo_stats_blocks(int rows) {
   return nb < 1 ? 1 : (nb > STATS_MAX_BLOCKS ? (int)STATS_MAX_BLOCKS : nb);
 }
 
-hipError_t launch_ppo_stats(const StatsArgs& a, int nblocks, hipStream_t s) {
-  hipLaunchKernelGGL(k_ppo_stats, dim3(nblocks), dim3(64 * st::WAVES), 0, s, a);
+hipError_t launch_ppo_stats(const StatsArgs& a, int nblocks, bool log_std, hipStream_t s) {
+  hipLaunchKernelGGL(log_std ? k_ppo_logstd : k_ppo_stats, dim3(nblocks), dim3(64 * st::WAVES), 0, s, a);
   return hipGetLastError();
 }
 
-hipError_t launch_stats_finish(const unsigned long long* partial, int nblocks, StatsRec* out,
+hipError_t launch_stats_finish(const unsigned long long* partial, int nblocks, bool log_std, void* out,
                                hipStream_t s) {
-  hipLaunchKernelGGL(k_stats_finish, dim3(1), dim3(64), 0, s, partial, nblocks, (unsigned long long*)out);
+  hipLaunchKernelGGL(k_stats_finish, dim3(1), dim3(64), 0, s, partial, nblocks,
+                     log_std ? (int)STATS_FIELDS_LS : (int)STATS_FIELDS, (unsigned long long*)out);
   return hipGetLastError();
 }
 

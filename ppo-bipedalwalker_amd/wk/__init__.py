@@ -49,6 +49,7 @@ EXPORTS = [
     "wk_get_bootstrap_values", "wk_set_bootstrap_values",
     "wk_policy_stats", "wk_update_stats_get", "wk_evaluate", "wk_evaluate_time",
     "wk_grad_norms_get", "wk_set_learning_rate", "wk_get_learning_rate",
+    "wk_get_log_std", "wk_set_log_std", "wk_set_log_std_adam", "wk_log_std_gradient",
 ]
 
 
@@ -63,7 +64,9 @@ def check_state(state):
 
 
 class WkConfig(C.Structure):
-    """wk_config: Hyperparameters.cs:80-121 names and defaults + batched extensions."""
+    """wk_config up to MaxGradNorm (its first 128 bytes): Hyperparameters.cs:80-121 names and
+    defaults + batched extensions.  The library reads and writes the whole wk_config, which is
+    WkConfigLogStd below: that is what default_config() returns and every call takes."""
     _fields_ = [
         ("GameSpeed", C.c_int), ("Iterations", C.c_int), ("MaxTimesteps", C.c_int),
         ("RoughFloor", C.c_int), ("Epochs", C.c_int), ("BatchSize", C.c_int),
@@ -77,6 +80,19 @@ class WkConfig(C.Structure):
         ("LanesPerWalker", C.c_int), ("NetworkKernels", C.c_int),
         ("ReturnsMode", C.c_int), ("TargetKL", C.c_float), ("MaxGradNorm", C.c_float),
     ]
+
+
+class WkConfigLogStd(WkConfig):
+    """wk_config as include/wk_api.h declares it: WkConfig's fields, then the five of the trained
+    log-std appended (a ctypes subclass lays its fields out after the base's; the base ends on an
+    8-byte boundary, so the offsets are the C struct's)."""
+    _fields_ = [
+        ("LearnLogStd", C.c_int), ("LogStdAlpha", C.c_float), ("EntropyCoef", C.c_float),
+        ("LogStdMin", C.c_float), ("LogStdMax", C.c_float),
+    ]
+
+
+assert C.sizeof(WkConfig) == WkConfigLogStd.LearnLogStd.offset == 128 and C.sizeof(WkConfigLogStd) == 152
 
 
 class HostSettings(C.Structure):
@@ -183,6 +199,27 @@ class GradNorms(C.Structure):
                 for k, _ in self._fields_ if k != "pad"}
 
 
+class LogStdGrad(C.Structure):
+    """wk_log_std_grad: the clipped surrogate's derivative by the scalar log-std over the
+    trajectory buffer (wk_log_std_gradient), host-divided"""
+    _fields_ = [("samples", C.c_int64), ("skipped", C.c_int64), ("grad_surrogate", C.c_double),
+                ("grad", C.c_double), ("z2_mean", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class LogStdState(C.Structure):
+    """wk_log_std_state: the policy's log-std and the state of its Adam step (wk_get_log_std)"""
+    _fields_ = [("log_std", C.c_float), ("std", C.c_float), ("t", C.c_int32), ("pad", C.c_int32),
+                ("m", C.c_double), ("v", C.c_double), ("entropy", C.c_double),
+                ("grad_last", C.c_double), ("steps", C.c_int64), ("clamped", C.c_int64),
+                ("nonfinite", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
 EVAL_MAX_EPISODES = 16  # WK_EVAL_MAX_EPISODES
 EVAL_FELL, EVAL_TIME_LIMIT, EVAL_SUCCESS, EVAL_UNFINISHED = 0, 1, 2, 3  # enum wk_eval_end
 EVAL_STARTS = {"reset": 0, "create": 1}  # wk_eval_args.start
@@ -266,9 +303,9 @@ def load_library(path=None):
     P, I, F, U32, U64 = C.c_void_p, C.c_int, C.c_float, C.c_uint32, C.c_uint64
     fp = C.POINTER(C.c_float)
     sig = {
-        "wk_config_defaults": (None, [C.POINTER(WkConfig)]),
+        "wk_config_defaults": (None, [C.POINTER(WkConfigLogStd)]),
         "wk_version": (C.c_char_p, []),
-        "wk_create": (I, [C.POINTER(WkConfig), I, I, U64, C.POINTER(P)]),
+        "wk_create": (I, [C.POINTER(WkConfigLogStd), I, I, U64, C.POINTER(P)]),
         "wk_destroy": (I, [P]),
         "wk_last_error": (C.c_char_p, [P]),
         "wk_sync": (I, [P]),
@@ -307,10 +344,10 @@ def load_library(path=None):
         "wk_checkpoint_save": (I, [P, C.c_char_p]),
         "wk_checkpoint_load": (I, [P, C.c_char_p]),
         "wk_host_settings_defaults": (None, [C.POINTER(HostSettings)]),
-        "wk_config_to_json": (I, [C.POINTER(WkConfig), C.POINTER(HostSettings), C.c_char_p, C.c_size_t]),
-        "wk_config_from_json": (I, [C.c_char_p, C.POINTER(WkConfig), C.POINTER(HostSettings)]),
-        "wk_config_save_json": (I, [C.c_char_p, C.POINTER(WkConfig), C.POINTER(HostSettings)]),
-        "wk_config_load_json": (I, [C.c_char_p, C.POINTER(WkConfig), C.POINTER(HostSettings)]),
+        "wk_config_to_json": (I, [C.POINTER(WkConfigLogStd), C.POINTER(HostSettings), C.c_char_p, C.c_size_t]),
+        "wk_config_from_json": (I, [C.c_char_p, C.POINTER(WkConfigLogStd), C.POINTER(HostSettings)]),
+        "wk_config_save_json": (I, [C.c_char_p, C.POINTER(WkConfigLogStd), C.POINTER(HostSettings)]),
+        "wk_config_load_json": (I, [C.c_char_p, C.POINTER(WkConfigLogStd), C.POINTER(HostSettings)]),
         "wk_collect_data": (I, [P, I]),
         "wk_episode_log_count": (I, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         "wk_episode_log_drain": (I, [P, P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -355,6 +392,10 @@ def load_library(path=None):
         "wk_grad_norms_get": (I, [P, C.POINTER(GradNorms)]),
         "wk_set_learning_rate": (I, [P, F]),
         "wk_get_learning_rate": (I, [P, fp]),
+        "wk_get_log_std": (I, [P, C.POINTER(LogStdState)]),
+        "wk_set_log_std": (I, [P, F]),
+        "wk_set_log_std_adam": (I, [P, C.c_double, C.c_double, I]),
+        "wk_log_std_gradient": (I, [P, C.POINTER(LogStdGrad)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -386,7 +427,7 @@ class WkError(RuntimeError):
 
 def default_config(**overrides):
     lib = load_library()
-    c = WkConfig()
+    c = WkConfigLogStd()  # (the whole wk_config; a bare WkConfig would be 24 bytes short)
     lib.wk_config_defaults(C.byref(c))
     for k, v in overrides.items():
         if not hasattr(c, k):
@@ -791,6 +832,30 @@ class Engine:
         a = C.c_float()
         self._chk(self.lib.wk_get_learning_rate(self.h, C.byref(a)), "wk_get_learning_rate")
         return a.value
+
+    def log_std(self):
+        """wk_get_log_std: the policy's log-std, std and entropy per dimension, and on a
+        LearnLogStd = 1 context the Adam state of the scalar and the last update's counters"""
+        s = LogStdState()
+        self._chk(self.lib.wk_get_log_std(self.h, C.byref(s)), "wk_get_log_std")
+        return s.as_dict()
+
+    def set_log_std(self, s):
+        """wk_set_log_std: the log-std every later launch uses (finite, inside (-5, 5), on a
+        LearnLogStd = 1 context inside [LogStdMin, LogStdMax]); keeps the scalar's Adam state"""
+        self._chk(self.lib.wk_set_log_std(self.h, float(s)), "wk_set_log_std")
+
+    def set_log_std_adam(self, m, v, t):
+        """wk_set_log_std_adam (LearnLogStd = 1): the scalar's Adam moments and step count"""
+        self._chk(self.lib.wk_set_log_std_adam(self.h, float(m), float(v), int(t)), "wk_set_log_std_adam")
+
+    def log_std_gradient(self):
+        """wk_log_std_gradient: the clipped surrogate's derivative by the log-std over the
+        trajectory buffer at the current weights and log-std, as a dict (it synchronises and
+        changes nothing)"""
+        g = LogStdGrad()
+        self._chk(self.lib.wk_log_std_gradient(self.h, C.byref(g)), "wk_log_std_gradient")
+        return g.as_dict()
 
     def evaluate(self, episodes=1, stochastic=False, start="reset", max_steps=0, poll=0, rng_step0=0,
                  records=False):
