@@ -133,8 +133,8 @@ DEV void floor_poly(Poly<4>& f) {
 // faster per vertex (two waves per SIMD compete for the issue slots, where a packed f32 op costs
 // more than the two plain ones it replaces and needs a wait state before its dependent read: 610
 // more VALU per wave-substep, the waves' wait share 0.275 -> 0.178), the quad kernels 9 % slower
-// (one wave per SIMD: the extra instructions lengthen its one dependent chain).  wk_physics.hip
-// sets WK_VERTEX_PACKED 0 for build part 1 only.
+// (one wave per SIMD: the extra instructions lengthen its one dependent chain).  Only
+// wk_env_pair.hip sets WK_VERTEX_PACKED 0.
 #ifndef WK_VERTEX_PACKED
 #define WK_VERTEX_PACKED 1
 #endif

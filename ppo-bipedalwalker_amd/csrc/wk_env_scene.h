@@ -1,7 +1,9 @@
-// wk_scene.inc -- scene props: Square / Triangle / Hexagon rigid bodies (with SmoothCorners)
-// added to every walker's body list after the floor.  Included by wk_physics.hip (same
-// translation unit: it reuses the walker state, joints, integrate and the traced walker
-// pairs of the one-lane mapping).
+// wk_env_scene.h -- scene props: Square / Triangle / Hexagon rigid bodies (with SmoothCorners)
+// added to every walker's body list after the floor (k_env_scene).  On top of wk_env_lane.h: it
+// reuses the walker state, joints, integrate, the traced walker pairs and the frame loop of the
+// one-lane mapping.  Four translation units instantiate it (given actions / policy, flat / rough
+// floor: wk_env_scene_*.hip), one each because a k_env_scene is ~280k instructions and they
+// dominate the build's wall time.
 //
 // Reference: Objects/RigidBodies/{Square,Triangle,Hexagon}.cs (FromSize), Skeleton.cs:33-53
 // (SmoothCorners: the vertex list is replaced, the centroid kept), RigidBody.cs:54-113,
@@ -16,6 +18,11 @@
 // compile-time-unrolled for a register polygon, a runtime loop for an LDS polygon.
 // Arithmetic is op-for-op the reference's (same association as resolve_pair / the oracle),
 // so walkers with props stay bit-exact with the CPU restatement.
+
+#pragma once
+#include "wk_env_lane.h"
+
+namespace wk {
 
 // an LDS-resident prop polygon: x(i) at b[64 i], y(i) at b[64 (n + i)], then cx, cy, vx,
 // vy, w, angle (SceneDev::off gives the first field of each prop)
@@ -710,7 +717,7 @@ DEV void substep_scene(EnvState& s, const Mat& mp, const Mat& mb, float dt, floa
   }
 }
 
-// the one-lane env-step kernel with props: k_env_step's frame loop (env_frames, wk_physics.hip,
+// the one-lane env-step kernel with props: k_env_step's frame loop (env_frames, wk_env_lane.h,
 // L = 1, no pacing, no counters) over substep_scene; its own part is the props -- A.props holds
 // [n][S.pstride] prop state, staged in LDS for the launch (with the boxes) and written back
 template <bool POLICY, bool RECORD, bool TRACE, bool ROUGH = false>
@@ -749,3 +756,18 @@ __global__ __launch_bounds__(64) void k_env_scene(EnvParams P, StepArgs A, Scene
   A.rng_t[e] = t;
   if (A.fault_out) A.fault_out[e] |= fault;
 }
+
+// host side: k_env_scene is instantiated where these are
+template <bool ROUGH>
+static void scene_given(int mode, const EnvParams& P, const StepArgs& A, const SceneDev& S, hipStream_t s) {
+  dim3 blk(64), grd((unsigned)((P.n_env + 63) / 64));
+  if (mode == 0) hipLaunchKernelGGL((k_env_scene<false, false, false, ROUGH>), grd, blk, 0, s, P, A, S);
+  else hipLaunchKernelGGL((k_env_scene<false, false, true, ROUGH>), grd, blk, 0, s, P, A, S);
+}
+template <bool ROUGH>
+static void scene_policy(int mode, const EnvParams& P, const StepArgs& A, const SceneDev& S, hipStream_t s) {
+  dim3 blk(64), grd((unsigned)((P.n_env + 63) / 64));
+  if (mode == 2) hipLaunchKernelGGL((k_env_scene<true, false, false, ROUGH>), grd, blk, 0, s, P, A, S);
+  else hipLaunchKernelGGL((k_env_scene<true, true, false, ROUGH>), grd, blk, 0, s, P, A, S);
+}
+}  // namespace wk

@@ -1,5 +1,5 @@
 // wk_kernels.h -- kernel argument blocks and host launch shims shared by
-// wk_physics.hip, wk_ppo.hip and wk_api.cpp.
+// the rollout units (wk_env*.hip), wk_ppo.hip and wk_api.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -68,7 +68,7 @@ struct StepArgs {
 };
 enum : int { PACE_SLOTS = 8 * 8 * 2 * 16 * 4 };  // XCC x SE x SH x CU x SIMD (HW_ID fields)
 
-// scene props (wk_scene.inc): Square / Triangle / Hexagon bodies after the floor, the same
+// scene props (wk_env_scene.h): Square / Triangle / Hexagon bodies after the floor, the same
 // shapes for every walker; per walker and prop k the state x[nv], y[nv], cx, cy, vx, vy, w,
 // angle starts at float off[k] of the walker's prop record
 enum : int {
@@ -121,6 +121,21 @@ static_assert(SLAB % 4 == 0 && SLAB >= NPARAM + 3, "slab layout");
 hipError_t launch_env_step(int mode, const EnvParams& P, const StepArgs& A, hipStream_t s);
 hipError_t launch_env_scene(int mode, const EnvParams& P, const StepArgs& A, const SceneDev& S,
                             hipStream_t s);
+// what the two dispatchers above (wk_env.hip) choose between: one kernel family per translation
+// unit, wk_env_pair.hip, wk_env_quad.hip, wk_env_side_rough.hip (k_env_side) and
+// wk_env_scene_{given,policy}[_rough].hip (k_env_scene), each built with its own switches and flags
+void launch_side_pair(int mode, const EnvParams& P, const StepArgs& A, hipStream_t s);
+void launch_side_quad(int mode, const EnvParams& P, const StepArgs& A, hipStream_t s);
+void launch_side_pair_rough(int mode, const EnvParams& P, const StepArgs& A, hipStream_t s);
+void launch_side_quad_rough(int mode, const EnvParams& P, const StepArgs& A, hipStream_t s);
+void launch_env_scene_given(int mode, const EnvParams& P, const StepArgs& A, const SceneDev& S,
+                            hipStream_t s);
+void launch_env_scene_policy(int mode, const EnvParams& P, const StepArgs& A, const SceneDev& S,
+                             hipStream_t s);
+void launch_env_scene_given_rough(int mode, const EnvParams& P, const StepArgs& A, const SceneDev& S,
+                                  hipStream_t s);
+void launch_env_scene_policy_rough(int mode, const EnvParams& P, const StepArgs& A, const SceneDev& S,
+                                   hipStream_t s);
 hipError_t launch_env_init(const EnvParams& P, float* st, const float* dx, const uint8_t* mask,
                            int post, hipStream_t s);
 hipError_t launch_get_obs(const EnvParams& P, const float* st, float* obs, hipStream_t s);

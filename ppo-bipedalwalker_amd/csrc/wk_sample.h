@@ -1,4 +1,4 @@
-// wk_sample.h -- the action sampler shared by the fused rollout kernels (wk_physics.hip) and the
+// wk_sample.h -- the action sampler shared by the fused rollout kernels (wk_env_*.h) and the
 // general networks' policy kernel (wk_net.hip): the noise depends on (seed, global env id,
 // env-step, dimension) only, never on the network.
 #pragma once

@@ -19,7 +19,7 @@
  * coefficient into the accumulator (17 register copies per rotation and about 20 VGPRs held
  * across the substep loop).  The same single FMA, the same operands: bit-identical
  * (tests/cpp/sincos_dev_check.hip).  The host build keeps the plain form, and so does a device
- * build that defines WK_SC_PLAIN_FMA (the rough-floor side kernels, wk_physics.hip). */
+ * build that defines WK_SC_PLAIN_FMA (the rough-floor side kernels, wk_env_side_rough.hip). */
 #if defined(__HIP_DEVICE_COMPILE__) && defined(__AMDGCN__) && !defined(WK_SC_PLAIN_FMA)
 WK_SC_FN double wk_sc_step(double p, double x2, double k) {
   double r;

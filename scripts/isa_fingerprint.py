@@ -2,7 +2,9 @@
 the .hip_fatbin section unbundled (as kernel_resources.py does), disassembled, and each kernel's
 instruction text hashed with addresses and branch offsets stripped.  Two builds whose kernels
 hash the same run the same instructions -- the check that a source clean-up (dead build
-options removed) left the product kernels unchanged.
+options removed, code moved between files) left the product kernels unchanged.  A kernel symbol
+found in a second code object is an error: translation units that share headers must not
+instantiate the same kernel twice.  LIB may also be one object of build/ (that unit's kernels).
 usage: isa_fingerprint.py LIB [OTHER_LIB]   (one lib: print; two: diff)"""
 import hashlib
 import os
@@ -42,6 +44,8 @@ def fingerprints(so):
                 m = re.match(r"^(\S+) <(.+)>:$", line) or re.match(r"^<(.+)>:$", line)
                 if m or line == "<end>:":
                     if name and body:
+                        if name in out:  # (two translation units instantiate the same kernel)
+                            raise RuntimeError(f"{so}: {name} is in a second code object")
                         out[name] = (hashlib.sha1("\n".join(body).encode()).hexdigest()[:16], len(body))
                     name, body = (m.groups()[-1] if m else None), []
                     continue

@@ -1,7 +1,7 @@
 """Static count of the instructions that do no arithmetic in the rollout's substep loop (CPU only).
 
-Compiles physics part 1 (the pair side kernels) to gfx950 assembly with the Makefile's own
-flags (target build/wk_physics.hip.p1.s), finds the substep loop of every k_env_side
+Compiles wk_env_pair.hip (the pair side kernels) to gfx950 assembly with the Makefile's own
+flags for it (target build/wk_env_pair.hip.s), finds the substep loop of every k_env_side
 instantiation -- the innermost loop that holds the rotations' double-precision FMA chains --
 and prints per loop: instructions, VALU, register-to-register copies (v_mov_b32 / v_mov_b64
 from a VGPR), s_nop count and wait states, and the basic blocks with the most of them.
@@ -18,7 +18,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "ppo-bipedalwalker_amd")
-ASM_TARGET = os.path.join("build", "wk_physics.hip.p1.s")
+ASM_TARGET = os.path.join("build", "wk_env_pair.hip.s")
 HEADLINE = "_ZN2wk10k_env_sideILb1ELb1ELb0ELi1ELb0EEEvNS_9EnvParamsENS_8StepArgsE"
 
 _LABEL = re.compile(r"^(\.LBB\d+_\d+):")
@@ -27,7 +27,7 @@ _F64_FMA = ("v_fma_f64", "v_fmac_f64")
 
 
 def build_asm(jobs=1):
-    """The assembly of physics part 1, built by the Makefile with the part's flags."""
+    """The assembly of wk_env_pair.hip, built by the Makefile with that unit's flags."""
     subprocess.run(["make", "-s", "-C", PKG, "-j", str(jobs), ASM_TARGET], check=True)
     return os.path.join(PKG, ASM_TARGET)
 

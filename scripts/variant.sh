@@ -2,10 +2,10 @@
 # Build an A/B variant library ppo-bipedalwalker_amd/libwk_<name>.so that recompiles only the
 # listed objects with extra flags and takes the rest from build/ (run `make` first):
 #   bash scripts/variant.sh <name> "<flags>" <target> [<target> ...]
-# A target is a source of csrc/ (wk_ppo_mfma.hip; wk_physics.hip: all eight parts) or the number
-# of one physics part (WK_PHYS_PART, see wk_physics.hip).  The objects are rebuilt by the
-# Makefile's own rules, so every one gets the flags it ships with (part 8 the default scheduler)
-# plus <flags>: as EXTRA for a source, as PHYS_EXTRA when only physics objects are rebuilt.
+# A target is a source of csrc/ (wk_ppo_mfma.hip; a rollout unit such as wk_env_pair.hip) or
+# wk_env for all eight rollout units.  The objects are rebuilt by the Makefile's own rules, so
+# every one gets the flags it ships with (wk_env_quad.hip the default scheduler) plus <flags>:
+# as PHYS_EXTRA when only rollout units are rebuilt, as EXTRA otherwise.
 # PHYS_SCHED in the environment replaces the physics scheduler option.
 set -eu
 cd "$(dirname "$0")/../ppo-bipedalwalker_amd"
@@ -15,10 +15,10 @@ rm -rf $B; mkdir -p $B; cp build/*.o $B/
 var=PHYS_EXTRA
 for t in "$@"; do
   case $t in
-    wk_physics.hip) rm -f $B/wk_physics.hip.p*.o;;
-    [1-8]) rm -f $B/wk_physics.hip.p$t.o;;
+    wk_env) rm -f $B/wk_env*.hip.o;;
     *) [ -f csrc/$t ] || { echo "no source csrc/$t" >&2; exit 2; }
-       rm -f $B/$t.o; var=EXTRA;;
+       rm -f $B/$t.o
+       case $t in wk_env*.hip) ;; *) var=EXTRA;; esac;;
   esac
 done
 make -s -j"${JOBS:-8}" BUILD=$B LIB=libwk_$name.so "$var=$flags"

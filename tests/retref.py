@@ -1,7 +1,7 @@
 """Restatement of the returns / advantages scans -- test infrastructure only (numpy).
 
   * returns32(mode, ...): float32, operation for operation as the kernels: mode 0 restates
-    k_returns (csrc/wk_physics.hip: the reference's PPOAgent.cs:414-498, whose GAE chain is never
+    k_returns (csrc/wk_env.hip: the reference's PPOAgent.cs:414-498, whose GAE chain is never
     carried and whose scans start from 0), mode 1 restates k_returns_std (csrc/wk_ppo.hip: chained
     GAE(lambda), the scan started from vlast).  The library is built without contraction, so every
     product and sum below rounds once, as on the GPU.

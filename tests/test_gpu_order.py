@@ -102,7 +102,7 @@ def test_rough_offset_order_follows_the_offsets(wk, tmp_path, lanes):
 
 @pytest.mark.parametrize("n,lanes,rough", [(40000, 2, 0), (40000, 2, 1), (20011, 1, 0), (3000, 16, 0)])
 def test_wave_pacing_is_invisible(wk, n, lanes, rough):
-    """the pacing of co-resident waves (wk_physics.hip pace_partner: per-SIMD progress slots,
+    """the pacing of co-resident waves (wk_env_state.h pace_partner: per-SIMD progress slots,
     s_setprio; the pair kernel and k_env_step) only decides which wave of a SIMD issues first: a
     context without it (WK_PACE=0, read at wk_create) gives the same trajectories, records and
     update"""

@@ -1,5 +1,5 @@
 """The flat-floor pair kernels take the polygons' vertices one at a time (WK_VERTEX_PACKED 0 in
-build part 1, csrc/wk_physics.hip / csrc/wk_device.h: move, rotate, proj_minmax, pole_own_minmax),
+csrc/wk_env_pair.hip, read by csrc/wk_device.h: move, rotate, proj_minmax, pole_own_minmax),
 every other kernel two at a time through v_pk_add_f32 / v_pk_mul_f32.  The two forms are the same
 IEEE operations per element, so the side kernels must still equal the one-lane kernel
 k_env_step<..., 1> (packed) bit for bit:

@@ -1,6 +1,6 @@
 """CPU: the rollout kernel's substep loop keeps its register-to-register copies and s_nop down.
 
-scripts/isa_overhead.py compiles physics part 1 to gfx950 assembly with the Makefile's flags and
+scripts/isa_overhead.py compiles wk_env_pair.hip to gfx950 assembly with the Makefile's flags and
 counts, in the headline kernel's substep loop, the v_mov_b32 / v_mov_b64 from a VGPR and the
 s_nop.  The parent of the copy cuts had 393 + 175 = 568 of them in 7,179 instructions
 (profiles/copy_cuts_ab.txt); a change that brings the coefficient copies of the rotation's
