@@ -355,6 +355,26 @@ typedef struct wk_grad_norms {
   int32_t pad[2];
 } wk_grad_norms;
 
+/* Reward normalisation (wk_reward_norm_*): the rewards the returns kernels read are scaled by the
+ * running standard deviation of the walkers' discounted returns, VecNormalize's reward scaling in
+ * a per-rollout form.  Switched on per context at run time, not part of wk_config. */
+typedef struct wk_reward_norm_args {
+  int32_t enable;   /* 0: off (returns read the raw rewards, as before); 1: on */
+  int32_t frozen;   /* 1: scale with the statistics as they are; update neither them nor acc */
+  float clip;       /* scaled rewards are clamped to [-clip, clip]; > 0, +inf = no clamp; default 10 */
+  float epsilon;    /* added to the variance; finite, >= 0; default 1e-8 */
+} wk_reward_norm_args;
+
+typedef struct wk_reward_norm {
+  int64_t count;            /* discounted-return samples in the running statistics */
+  double mean, m2, var;     /* running mean, sum of squared deviations, m2 / count (0 when count is 0) */
+  float scale;              /* the factor the last pass used; 1 before any */
+  float clip, epsilon;
+  int32_t enabled, frozen, pad;
+  int64_t rows, clipped, nonfinite; /* of the last pass: rows scaled, rows the clamp changed,
+                                       samples left out of the statistics */
+} wk_reward_norm;
+
 /* one finished episode (data collection) */
 typedef struct wk_episode_rec {
   float total_reward;  /* (float) of the double sum of its rewards, like Enumerable.Sum */
@@ -588,6 +608,62 @@ int wk_get_log_std(wk_ctx* ctx, wk_log_std_state* out);
 int wk_set_log_std(wk_ctx* ctx, float log_std);
 int wk_set_log_std_adam(wk_ctx* ctx, double m, double v, int t);
 int wk_log_std_gradient(wk_ctx* ctx, wk_log_std_grad* out);
+
+/* Reward normalisation (wk_reward_norm_args, wk_reward_norm).  An enabled context keeps, on the
+ * device, acc[n_env] (fp32: each walker's running discounted return, carried across rollouts, 0 at
+ * enable), the running (count, mean, m2) in double, the fp32 scale and a second reward buffer
+ * trs[T][n]; wk_rollout stays asynchronous.
+ *
+ * The full pass runs inside wk_rollout after the physics and before the bootstrap values and the
+ * returns (three launches, timed in wk_profile's returns slot), and alone as wk_reward_norm_update:
+ *   scan    per walker e, forward over the rows t: x = r[t][e] + (acc * Gamma) in fp32 (uncontracted,
+ *           as the returns kernel forms r + disc * Gamma).  A finite x is one sample -- 1, (double)x
+ *           and (double)x (double)x go to the batch's count and sums -- and becomes acc; any other x
+ *           is counted in `nonfinite` and zeroes acc.  A terminal row then zeroes acc.
+ *   finish  mean_b = s1 / cnt_b, m2_b = max(0, s2 - s1 mean_b); merged into the running statistics
+ *           in double by Chan's formula (delta = mean_b - mean, tot = count + cnt_b, mean += delta
+ *           cnt_b / tot, m2 += m2_b + delta delta count cnt_b / tot, count = tot; skipped when cnt_b
+ *           is 0); var = m2 / count and scale = (float)(1 / sqrt(var + (double)epsilon)), 1 when
+ *           count is 0 or the result is not finite and positive.
+ *   apply   trs = r * scale, one fp32 product, then clamped: |y| > clip gives copysignf(clip, y) and
+ *           is counted in `clipped`.  A NaN stays NaN; +-inf clamps to +-clip.
+ * The sums are ordered (no floating-point atomics): the same inputs give the same bytes.  The
+ * scale already includes the rollout being scaled, so the first rollout is scaled too: a
+ * per-rollout form of VecNormalize's per-step scaling.
+ *
+ * Only the returns kernels read trs (wk_rollout, wk_compute_returns, wk_ppo_update's stale
+ * returns): returns, advantages, value targets and bootstrap values are then in scaled units.  The
+ * episode log, wk_rollout_stats_get, wk_get_trajectory's rewards, wk_count_events, wk_evaluate,
+ * wk_step* and the fault bits keep the raw rewards, and none of them touches acc.
+ *
+ * wk_reward_norm_config: NaNs, clip <= 0, a negative or non-finite epsilon, enable or frozen outside
+ * 0..1 are WK_ERR_ARG and change nothing.  The first enable allocates and zeroes the state; a
+ * disable keeps it for a later enable.  Every change marks the returns stale and, with a trajectory
+ * in the buffer, re-runs the apply step.  WK_ERR_CONFIG when enabling on a context with a
+ * communicator, and from the four wk_comm_* initialisers on an enabled context (every rank would
+ * scale by its own shard's statistics).
+ * frozen = 1 makes every pass the apply step alone.  wk_set_trajectory on an enabled context runs
+ * the apply step alone with the current scale (foreign data: nothing is learned from it); a host
+ * that wants it learned calls wk_reward_norm_update once afterwards (twice counts the data twice).
+ * wk_reward_norm_get: any context; one never enabled reports zeros and scale 1.  It synchronises
+ * the stream.  wk_reward_norm_set replaces the statistics (count >= 0, a finite mean, a finite m2 >=
+ * 0, else WK_ERR_ARG) and forms the scale by the same formula on the host; the returns go stale and
+ * the apply step runs again.  wk_reward_norm_set / _get_acc / _set_acc / _update and
+ * wk_get_scaled_rewards are WK_ERR_STATE on a context never enabled, _update and
+ * wk_get_scaled_rewards also without a trajectory.
+ * wk_reset zeroes acc of the walkers it resets; wk_set_state leaves acc alone.  wk_snapshot saves
+ * and restores acc, the statistics and the scale on an enabled context.  An enabled context writes
+ * checkpoint version 7 -- after every earlier section the arguments, (count, mean, m2, scale) and
+ * acc[n_env] -- and loads only such files; a context not enabled writes versions 4 / 5 / 6 byte for
+ * byte as before and refuses version 7 (enable first). */
+void wk_reward_norm_defaults(wk_reward_norm_args* args);
+int wk_reward_norm_config(wk_ctx* ctx, const wk_reward_norm_args* args);
+int wk_reward_norm_get(wk_ctx* ctx, wk_reward_norm* out);
+int wk_reward_norm_set(wk_ctx* ctx, int64_t count, double mean, double m2);
+int wk_reward_norm_get_acc(wk_ctx* ctx, float* acc /* n_env */);
+int wk_reward_norm_set_acc(wk_ctx* ctx, const float* acc /* n_env */);
+int wk_reward_norm_update(wk_ctx* ctx);
+int wk_get_scaled_rewards(wk_ctx* ctx, float* out /* T_valid * n_env */);
 
 /* Policy evaluation (the engine's counterpart of the console's _bestDistance and last-episode
  * average reward, Environment.cs:55-60,119): every walker of the context plays `episodes` COMPLETE

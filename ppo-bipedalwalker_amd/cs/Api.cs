@@ -156,6 +156,49 @@ namespace NEA.Walker
             Wk.Ok(ctx, Wk.wk_log_std_gradient(ctx, out var g), "Exception while reading the log standard deviation's gradient", log) ? g : null;
     }
 
+    // Reward normalisation (the reference trains on the raw rewards, Environment.cs:148-154): the
+    // rewards the returns read are scaled by the running std of the walkers' discounted returns;
+    // the trajectory's own rewards, the episode log and the evaluation stay raw.  Switched on per
+    // context at run time.  null / false on failure, logged
+    public static class RewardNorm
+    {
+        public static bool Configure(IntPtr ctx, bool enable = true, float clip = 10.0f, float epsilon = 1e-8f, bool frozen = false,
+                                     Action<string>? log = null)
+        {
+            var a = new WkRewardNormArgs();
+            Wk.wk_reward_norm_defaults(ref a);
+            a.Enable = enable ? 1 : 0; a.Frozen = frozen ? 1 : 0; a.Clip = clip; a.Epsilon = epsilon;
+            return Wk.Ok(ctx, Wk.wk_reward_norm_config(ctx, ref a), "Exception while configuring the reward normalisation", log);
+        }
+
+        public static WkRewardNorm? State(IntPtr ctx, Action<string>? log = null) =>
+            Wk.Ok(ctx, Wk.wk_reward_norm_get(ctx, out var s), "Exception while reading the reward normalisation", log) ? s : null;
+
+        public static bool SetState(IntPtr ctx, long count, double mean, double m2, Action<string>? log = null) =>
+            Wk.Ok(ctx, Wk.wk_reward_norm_set(ctx, count, mean, m2), "Exception while setting the reward statistics", log);
+
+        public static float[]? Acc(IntPtr ctx, Action<string>? log = null)
+        {
+            var a = new float[Wk.wk_num_envs(ctx)];
+            return Wk.Ok(ctx, Wk.wk_reward_norm_get_acc(ctx, a), "Exception while reading the running returns", log) ? a : null;
+        }
+
+        public static bool SetAcc(IntPtr ctx, float[] acc, Action<string>? log = null) =>
+            acc.Length == Wk.wk_num_envs(ctx) &&
+            Wk.Ok(ctx, Wk.wk_reward_norm_set_acc(ctx, acc), "Exception while setting the running returns", log);
+
+        // the full pass on the current trajectory buffer (after wk_set_trajectory, whose data is scaled but not learned)
+        public static bool Update(IntPtr ctx, Action<string>? log = null) =>
+            Wk.Ok(ctx, Wk.wk_reward_norm_update(ctx), "Exception while updating the reward statistics", log);
+
+        // the [horizon][n] rewards the returns kernels read; horizon = the rows of the trajectory buffer
+        public static float[]? ScaledRewards(IntPtr ctx, int horizon, Action<string>? log = null)
+        {
+            var r = new float[(long)horizon * Wk.wk_num_envs(ctx)];
+            return Wk.Ok(ctx, Wk.wk_get_scaled_rewards(ctx, r), "Exception while reading the scaled rewards", log) ? r : null;
+        }
+    }
+
     // How good the policy is now (the counterpart of the console's _bestDistance and last-episode
     // average reward, Environment.cs:55-60,119): every walker plays complete episodes under the
     // current actor -- its mean action unless args.Stochastic -- on a private copy of the walker

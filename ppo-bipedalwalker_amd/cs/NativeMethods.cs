@@ -191,6 +191,26 @@ public struct WkLogStdState
     public long Steps, Clamped, Nonfinite;
 }
 
+// wk_reward_norm_config: Enable 1 scales the rewards the returns kernels read by the running std of the walkers' discounted
+// returns (clamped to +-Clip, Epsilon added to the variance); Frozen 1 scales with the statistics as they are
+[StructLayout(LayoutKind.Sequential)]
+public struct WkRewardNormArgs
+{
+    public int Enable, Frozen;
+    public float Clip, Epsilon;
+}
+
+// wk_reward_norm_get: the running statistics, the scale the last pass used, the arguments and that pass's counters
+[StructLayout(LayoutKind.Sequential)]
+public struct WkRewardNorm
+{
+    public long Count;
+    public double Mean, M2, Var;
+    public float Scale, Clip, Epsilon;
+    public int Enabled, Frozen, Pad;
+    public long Rows, Clipped, Nonfinite;
+}
+
 // wk_evaluate: complete episodes under the current actor on a private copy of the walkers
 [StructLayout(LayoutKind.Sequential)]
 public struct WkEvalArgs
@@ -321,6 +341,14 @@ public static class Wk
     [DllImport(Lib)] public static extern int wk_set_log_std(IntPtr ctx, float logStd);
     [DllImport(Lib)] public static extern int wk_set_log_std_adam(IntPtr ctx, double m, double v, int t);
     [DllImport(Lib)] public static extern int wk_log_std_gradient(IntPtr ctx, out WkLogStdGrad grad);
+    [DllImport(Lib)] public static extern void wk_reward_norm_defaults(ref WkRewardNormArgs args);
+    [DllImport(Lib)] public static extern int wk_reward_norm_config(IntPtr ctx, ref WkRewardNormArgs args);
+    [DllImport(Lib)] public static extern int wk_reward_norm_get(IntPtr ctx, out WkRewardNorm state);
+    [DllImport(Lib)] public static extern int wk_reward_norm_set(IntPtr ctx, long count, double mean, double m2);
+    [DllImport(Lib)] public static extern int wk_reward_norm_get_acc(IntPtr ctx, [Out] float[] acc);
+    [DllImport(Lib)] public static extern int wk_reward_norm_set_acc(IntPtr ctx, float[] acc);
+    [DllImport(Lib)] public static extern int wk_reward_norm_update(IntPtr ctx);
+    [DllImport(Lib)] public static extern int wk_get_scaled_rewards(IntPtr ctx, [Out] float[] rewards);
     [DllImport(Lib)] public static extern int wk_evaluate(IntPtr ctx, ref WkEvalArgs args, out WkEvalStats stats, [Out] WkEvalRec[]? recs);
     [DllImport(Lib)] public static extern int wk_evaluate_time(IntPtr ctx, int reps, out double stepMs, out double foldMs);
     [DllImport(Lib)] public static extern int wk_train_batch(IntPtr ctx, int B, float bDiv, float[] states, float[] actions, float[] logpOld, float[] returns, float[] adv, out float criticDiag, out float actorDiag, float[]? gradsOut, int applyAdam, out int skipped);

@@ -239,6 +239,45 @@ class PPOAgent {
       LogError(std::string("Exception while reading the log standard deviation's gradient: ") + wk_last_error(ctx_));
     return g;
   }
+  // Reward normalisation: the rewards the returns read are scaled by the running std of the
+  // walkers' discounted returns (switched on per context at run time; the trajectory's own
+  // rewards, the episode log and Evaluate stay raw).  A zeroed record / empty vector on failure
+  void RewardNorm(bool enable = true, float clip = 10.0f, float epsilon = 1e-8f, bool frozen = false) {
+    wk_reward_norm_args a;
+    wk_reward_norm_defaults(&a);
+    a.enable = enable ? 1 : 0; a.frozen = frozen ? 1 : 0; a.clip = clip; a.epsilon = epsilon;
+    if (wk_reward_norm_config(ctx_, &a) != WK_OK)
+      LogError(std::string("Exception while configuring the reward normalisation: ") + wk_last_error(ctx_));
+  }
+  wk_reward_norm RewardNormState() {
+    wk_reward_norm s{};
+    if (wk_reward_norm_get(ctx_, &s) != WK_OK) LogError(wk_last_error(ctx_));
+    return s;
+  }
+  void SetRewardNormState(int64_t count, double mean, double m2) {
+    if (wk_reward_norm_set(ctx_, count, mean, m2) != WK_OK)
+      LogError(std::string("Exception while setting the reward statistics: ") + wk_last_error(ctx_));
+  }
+  std::vector<float> RewardAcc() {
+    std::vector<float> a((size_t)wk_num_envs(ctx_));
+    if (wk_reward_norm_get_acc(ctx_, a.data()) != WK_OK) { LogError(wk_last_error(ctx_)); a.clear(); }
+    return a;
+  }
+  void SetRewardAcc(const std::vector<float>& a) {
+    if (a.size() != (size_t)wk_num_envs(ctx_) || wk_reward_norm_set_acc(ctx_, a.data()) != WK_OK)
+      LogError(std::string("Exception while setting the running returns: ") + wk_last_error(ctx_));
+  }
+  // the full pass on the current trajectory buffer (after wk_set_trajectory, whose data is scaled
+  // but not learned)
+  void RewardNormUpdate() {
+    if (wk_reward_norm_update(ctx_) != WK_OK)
+      LogError(std::string("Exception while updating the reward statistics: ") + wk_last_error(ctx_));
+  }
+  std::vector<float> ScaledRewards(int horizon) {
+    std::vector<float> r((size_t)horizon * (size_t)wk_num_envs(ctx_));
+    if (wk_get_scaled_rewards(ctx_, r.data()) != WK_OK) { LogError(wk_last_error(ctx_)); r.clear(); }
+    return r;
+  }
   // How good the policy is now (the counterpart of the console's _bestDistance and last-episode
   // average reward, Environment.cs:55-60,119): every walker plays complete episodes under the
   // current actor (its mean action unless args.stochastic) on a private copy of the walker state;

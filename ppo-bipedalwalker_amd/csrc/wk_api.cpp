@@ -83,6 +83,18 @@ struct wk_ctx {
   double ls_m = 0.0, ls_v = 0.0, ls_grad_last = 0.0;
   int ls_t = 0;
   int64_t ls_steps = 0, ls_clamped = 0, ls_nonfinite = 0;
+  // reward normalisation (wk_reward_norm_config): nothing is allocated before the first enable.
+  // rn_acc [n] the walkers' running discounted returns, rn_rec the statistics and the scale, trs
+  // [T][n] the scaled rewards the returns kernels read, rn_partial the scan's tile partials,
+  // rn_snap wk_snapshot's copy of rn_acc and rn_rec
+  bool rn_ever = false;
+  int rn_on = 0, rn_frozen = 0;
+  float rn_clip = 10.0f, rn_eps = 1e-8f;
+  float* rn_acc = nullptr; float* trs = nullptr;
+  wk::RnormRec* rn_rec = nullptr;
+  unsigned long long* rn_partial = nullptr;
+  char* rn_snap = nullptr;
+  bool rn_snap_valid = false;
   // data collection (ConsoleRenderer.AddTotalEpisodeReward / AddCriticLoss / AddActorLoss)
   int collect = 1;
   uint32_t rollout_steps = 0;  // env-steps taken by wk_rollout so far (episode log clock)
@@ -659,6 +671,7 @@ int wk_reset(wk_ctx* c, const uint8_t* mask) {
   // Environment.Reset re-creates the walker after the floor (post-reset body order)
   HIPCHK(c, wk::launch_env_init(c->P, c->st, c->dxoff, dmask, 1, c->stream));
   HIPCHK(c, wk::launch_episode_reset(c->n, dmask, c->ep_acc, c->ep_len, c->stream));
+  if (c->rn_acc) HIPCHK(c, wk::launch_rnorm_reset(c->n, dmask, c->rn_acc, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return WK_OK;
 }
@@ -1327,20 +1340,33 @@ static int bootstrap_values(wk_ctx* c) {
   return WK_OK;
 }
 
+// Reward normalisation over the valid trajectory buffer (wk_rnorm.hip), timed in the returns slot.
+// learn: the full pass -- the scan carries rn_acc, the finish step merges the batch into rn_rec and
+// forms the scale, the apply step writes trs; otherwise, and on a frozen context, the apply step
+// alone with the scale as it is.
+static int rnorm_pass(wk_ctx* c, bool learn) {
+  ProfScope ps(c, PK_RET);
+  HIPCHK(c, wk::launch_rnorm_pass(c->n, c->T_valid, c->cfg.Gamma, c->rn_clip, c->rn_eps,
+                                  learn && !c->rn_frozen, c->tr, c->td, c->rn_acc, c->rn_partial,
+                                  c->rn_rec, c->trs, c->stream));
+  return WK_OK;
+}
+
 static int returns_impl(wk_ctx* c) {
   if (c->cfg.ReturnsMode == 1 && !c->vlast_valid) {
     SETERR(c, "ReturnsMode 1: the trajectory has no bootstrap values -- call wk_set_bootstrap_values "
               "(zeros for complete episodes, wk_value of the next observations at a cut)");
     return WK_ERR_STATE;
   }
+  const float* rew = c->rn_on ? c->trs : c->tr;  // (reward normalisation: the scaled rewards)
   {
     ProfScope ps(c, PK_RET);
     if (c->cfg.ReturnsMode == 1)
       HIPCHK(c, wk::launch_returns_std(c->n, c->T_valid, c->cfg.UseGAE, c->cfg.Gamma, c->cfg.Lambda,
-                                       c->tr, c->tv, c->td, c->vlast, c->tret, c->tadv, c->stream));
+                                       rew, c->tv, c->td, c->vlast, c->tret, c->tadv, c->stream));
     else
       HIPCHK(c, wk::launch_returns(c->n, c->T_valid, c->cfg.UseGAE, c->cfg.Gamma, c->cfg.Lambda,
-                                   c->tr, c->tv, c->td, c->tret, c->tadv, c->stream));
+                                   rew, c->tv, c->td, c->tret, c->tadv, c->stream));
   }
   if (c->cfg.NormalizeAdvantages)
     HIPCHK(c, wk::launch_normalize(c->tadv, c->n * c->T_valid, c->cfg.Epsilon, c->stream));
@@ -1365,6 +1391,8 @@ int wk_rollout(wk_ctx* c, int horizon) {
     HIPCHK(c, wk::launch_episode_log(e, c->stream));
   }
   c->rollout_steps += (uint32_t)horizon;
+  if (c->rn_on)
+    if (int r = rnorm_pass(c, true)) return r;
   if (c->cfg.ReturnsMode == 1)
     if (int r = bootstrap_values(c)) return r;
   return returns_impl(c);
@@ -1420,6 +1448,8 @@ int wk_set_trajectory(wk_ctx* c, int horizon, const float* s, const float* a, co
   c->T_valid = horizon;
   c->returns_valid = false;
   c->vlast_valid = false;
+  // foreign data: scaled with the scale as it is, nothing learned (wk_reward_norm_update learns it)
+  if (c->rn_on) return rnorm_pass(c, false);
   return WK_OK;
 }
 
@@ -1448,6 +1478,158 @@ int wk_set_bootstrap_values(wk_ctx* c, const float* v) {
   HIPCHK(c, hipMemcpy(c->vlast, v, sizeof(float) * c->n, hipMemcpyHostToDevice));
   c->vlast_valid = true;
   c->returns_valid = false;
+  return WK_OK;
+}
+
+// ---------------- reward normalisation (wk_rnorm.hip) ----------------
+static_assert(sizeof(wk_reward_norm) == sizeof(wk::RnormRec), "wk_reward_norm layout");
+
+// var and scale from (count, m2, epsilon): the finish kernel's formula, on the host
+static void rnorm_scale(wk::RnormRec& r, float epsilon) {
+  r.var = r.count > 0 ? r.m2 / (double)r.count : 0.0;
+  r.scale = 1.0f;
+  if (r.count > 0) {
+    const float sc = (float)(1.0 / std::sqrt(r.var + (double)epsilon));
+    if (std::isfinite(sc) && sc > 0.0f) r.scale = sc;
+  }
+}
+
+static int rnorm_need(wk_ctx* c, const char* fn) {
+  if (c->rn_ever) return WK_OK;
+  SETERR(c, "%s: reward normalisation was never enabled on this context (wk_reward_norm_config)", fn);
+  return WK_ERR_STATE;
+}
+
+// the statistics changed under a trajectory: its returns are stale and its scaled rewards follow
+static int rnorm_changed(wk_ctx* c) {
+  if (c->T_valid <= 0) return WK_OK;
+  c->returns_valid = false;
+  return c->rn_on ? rnorm_pass(c, false) : WK_OK;
+}
+
+void wk_reward_norm_defaults(wk_reward_norm_args* a) {
+  if (!a) return;
+  a->enable = 0;
+  a->frozen = 0;
+  a->clip = 10.0f;
+  a->epsilon = 1e-8f;
+}
+
+int wk_reward_norm_config(wk_ctx* c, const wk_reward_norm_args* a) {
+  DevGuard dg_(c);
+  if (!c || !a) return WK_ERR_ARG;
+  if (a->enable < 0 || a->enable > 1 || a->frozen < 0 || a->frozen > 1 || !(a->clip > 0.0f) ||
+      !std::isfinite(a->epsilon) || a->epsilon < 0.0f) {
+    SETERR(c, "wk_reward_norm_config: enable and frozen are 0 or 1, clip > 0 (+inf: no clamp), epsilon "
+              "finite and >= 0 (got %d, %d, %g, %g)", a->enable, a->frozen, (double)a->clip, (double)a->epsilon);
+    return WK_ERR_ARG;
+  }
+  if (a->enable && (c->comm || c->host_ar || c->ipc || c->xch)) {
+    SETERR(c, "reward normalisation is one GPU: this context has a gradient exchange, and every rank "
+              "would scale by its own shard's statistics");
+    return WK_ERR_CONFIG;
+  }
+  if (a->enable && !c->rn_ever) {  // the first enable: acc 0, no samples, scale 1
+    const size_t n = c->n;
+    if (!c->rn_acc) HIPCHK(c, dev_alloc(c, &c->rn_acc, sizeof(float) * n));
+    if (!c->trs) HIPCHK(c, dev_alloc(c, &c->trs, sizeof(float) * n * c->T));
+    if (!c->rn_rec) HIPCHK(c, dev_alloc(c, &c->rn_rec, sizeof(wk::RnormRec)));
+    if (!c->rn_partial)
+      HIPCHK(c, dev_alloc(c, &c->rn_partial, sizeof(unsigned long long) * wk::RNORM_FIELDS * wk::rnorm_tiles(c->n)));
+    wk::RnormRec r{};
+    r.scale = 1.0f;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemset(c->rn_acc, 0, sizeof(float) * n));
+    HIPCHK(c, hipMemcpy(c->rn_rec, &r, sizeof r, hipMemcpyHostToDevice));
+    c->rn_ever = true;
+  }
+  const bool changed = a->enable != c->rn_on || a->frozen != c->rn_frozen ||
+                       memcmp(&a->clip, &c->rn_clip, sizeof(float)) != 0 ||
+                       memcmp(&a->epsilon, &c->rn_eps, sizeof(float)) != 0;
+  if (c->rn_ever && a->epsilon != c->rn_eps) {  // the scale follows its epsilon
+    wk::RnormRec r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(&r, c->rn_rec, sizeof r, hipMemcpyDeviceToHost));
+    rnorm_scale(r, a->epsilon);
+    HIPCHK(c, hipMemcpy(c->rn_rec, &r, sizeof r, hipMemcpyHostToDevice));
+  }
+  c->rn_on = a->enable;
+  c->rn_frozen = a->frozen;
+  c->rn_clip = a->clip;
+  c->rn_eps = a->epsilon;
+  return changed && c->rn_ever ? rnorm_changed(c) : WK_OK;
+}
+
+int wk_reward_norm_get(wk_ctx* c, wk_reward_norm* out) {
+  DevGuard dg_(c);
+  if (!c || !out) return WK_ERR_ARG;
+  memset(out, 0, sizeof(*out));
+  out->scale = 1.0f;
+  if (!c->rn_ever) return WK_OK;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(out, c->rn_rec, sizeof(*out), hipMemcpyDeviceToHost));
+  out->clip = c->rn_clip;
+  out->epsilon = c->rn_eps;
+  out->enabled = c->rn_on;
+  out->frozen = c->rn_frozen;
+  out->pad = 0;
+  return WK_OK;
+}
+
+int wk_reward_norm_set(wk_ctx* c, int64_t count, double mean, double m2) {
+  DevGuard dg_(c);
+  if (!c) return WK_ERR_ARG;
+  if (int r = rnorm_need(c, "wk_reward_norm_set")) return r;
+  if (count < 0 || !std::isfinite(mean) || !std::isfinite(m2) || m2 < 0.0) {
+    SETERR(c, "wk_reward_norm_set: count >= 0, a finite mean and a finite m2 >= 0 (got %lld, %g, %g)",
+           (long long)count, mean, m2);
+    return WK_ERR_ARG;
+  }
+  wk::RnormRec r;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(&r, c->rn_rec, sizeof r, hipMemcpyDeviceToHost));
+  r.count = count;
+  r.mean = mean;
+  r.m2 = m2;
+  rnorm_scale(r, c->rn_eps);
+  HIPCHK(c, hipMemcpy(c->rn_rec, &r, sizeof r, hipMemcpyHostToDevice));
+  return rnorm_changed(c);
+}
+
+int wk_reward_norm_get_acc(wk_ctx* c, float* acc) {
+  DevGuard dg_(c);
+  if (!c || !acc) return WK_ERR_ARG;
+  if (int r = rnorm_need(c, "wk_reward_norm_get_acc")) return r;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(acc, c->rn_acc, sizeof(float) * c->n, hipMemcpyDeviceToHost));
+  return WK_OK;
+}
+
+int wk_reward_norm_set_acc(wk_ctx* c, const float* acc) {
+  DevGuard dg_(c);
+  if (!c || !acc) return WK_ERR_ARG;
+  if (int r = rnorm_need(c, "wk_reward_norm_set_acc")) return r;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(c->rn_acc, acc, sizeof(float) * c->n, hipMemcpyHostToDevice));
+  return WK_OK;
+}
+
+int wk_reward_norm_update(wk_ctx* c) {
+  DevGuard dg_(c);
+  if (!c) return WK_ERR_ARG;
+  if (int r = rnorm_need(c, "wk_reward_norm_update")) return r;
+  if (c->T_valid <= 0) { SETERR(c, "wk_reward_norm_update: no trajectory recorded"); return WK_ERR_STATE; }
+  c->returns_valid = false;
+  return rnorm_pass(c, true);
+}
+
+int wk_get_scaled_rewards(wk_ctx* c, float* out) {
+  DevGuard dg_(c);
+  if (!c || !out) return WK_ERR_ARG;
+  if (int r = rnorm_need(c, "wk_get_scaled_rewards")) return r;
+  if (c->T_valid <= 0) { SETERR(c, "wk_get_scaled_rewards: no trajectory recorded"); return WK_ERR_STATE; }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(out, c->trs, sizeof(float) * c->n * c->T_valid, hipMemcpyDeviceToHost));
   return WK_OK;
 }
 
@@ -2232,6 +2414,12 @@ int wk_minibatch_gradient(wk_ctx* c, int B, float b_div, const float* s, const f
 }
 
 static int refuse_comm(wk_ctx* c) {
+  // ranks scaling their rewards by their own shards' statistics would train on different targets
+  if (c->rn_on) {
+    SETERR(c, "the multi-GPU gradient exchange refuses a context with reward normalisation enabled: "
+              "every rank would scale by its own shard's statistics");
+    return WK_ERR_CONFIG;
+  }
   // ranks that stop on their own shards' KL would desert each other mid-exchange
   if (c->cfg.TargetKL > 0.0f) {
     SETERR(c, "the multi-GPU gradient exchange refuses a TargetKL > 0 context: every rank would "
@@ -2521,6 +2709,22 @@ int wk_snapshot(wk_ctx* c, int op) {
                                hipMemcpyDeviceToDevice, c->stream));
     q += (g.bytes + 255) & ~(size_t)255;
   }
+  // reward normalisation, on an enabled context: the walkers' running returns, then the record
+  // (statistics and scale); a snapshot taken before the first enable holds none and restores none
+  if (c->rn_on && (op == 0 || c->rn_snap_valid)) {
+    const size_t acc_bytes = (sizeof(float) * n + 255) & ~(size_t)255;
+    if (!c->rn_snap) HIPCHK(c, dev_alloc(c, &c->rn_snap, acc_bytes + sizeof(wk::RnormRec)));
+    const Seg rn[] = {{c->rn_acc, sizeof(float) * n}, {c->rn_rec, sizeof(wk::RnormRec)}};
+    char* at = c->rn_snap;
+    for (const Seg& g : rn) {
+      HIPCHK(c, hipMemcpyAsync(op == 0 ? (void*)at : g.p, op == 0 ? g.p : (const void*)at, g.bytes,
+                               hipMemcpyDeviceToDevice, c->stream));
+      at += acc_bytes;
+    }
+    if (op == 0) c->rn_snap_valid = true;
+  } else if (op == 0) {
+    c->rn_snap_valid = false;
+  }
   if (op == 0) {
     c->snap_valid = true;
   } else {
@@ -2709,6 +2913,20 @@ struct CkptLogStd {
 };
 #pragma pack(pop)
 static_assert(sizeof(CkptLogStd) == 24, "checkpoint log-std section");
+// 7: a context with reward normalisation enabled, of either kernel family, with or without a
+// trained log-std (CkptExt.reserved0 / reserved1 tell which, as in version 6): after the scene
+// section, at the end of the file, this record and acc[n_env].  A context not enabled still
+// writes version 4, 5 or 6, byte for byte as before
+const uint32_t kCkptVersionRnorm = 7;
+struct CkptRnorm {
+  int32_t enable, frozen;
+  float clip, epsilon;
+  int64_t count;
+  double mean, m2;
+  float scale;
+  int32_t pad;
+};
+static_assert(sizeof(CkptRnorm) == 48, "checkpoint reward-normalisation section");
 // The file's fixed sections, in file order, between its variable head (header, CkptExt, the
 // version-5 network section) and its scene section: the only place that knows the order
 std::array<Seg, 9> ckpt_sections(const wk_ctx* c) {
@@ -2828,7 +3046,9 @@ int wk_checkpoint_save(wk_ctx* c, const char* path) {
   if (!c || !path) return WK_ERR_ARG;
   const size_t n = c->n;
   const bool learn = c->cfg.LearnLogStd == 1;
-  CkptHeader h{kCkptMagic, learn ? kCkptVersionLogStd : (c->general ? kCkptVersionNet : kCkptVersion),
+  const bool rnorm = c->rn_on != 0;
+  CkptHeader h{kCkptMagic,
+               rnorm ? kCkptVersionRnorm : learn ? kCkptVersionLogStd : (c->general ? kCkptVersionNet : kCkptVersion),
                (uint32_t)n, (uint32_t)wk::NSTATE,
                (uint32_t)c->np, (uint32_t)c->adam_t, c->seed, c->cfg.EnvOffset, c->cfg.Iterations,
                c->cfg.MaxTimesteps, c->rollout_steps};
@@ -2840,7 +3060,8 @@ int wk_checkpoint_save(wk_ctx* c, const char* path) {
     const CkptLogStd ls{c->P.log_std, c->ls_t, c->ls_m, c->ls_v};
     nets.append((const char*)&ls, sizeof ls);
   }
-  std::vector<char> buf(sizeof h + sizeof ext + nets.size() + ckpt_offset(c, nullptr) + scene_bytes);
+  const size_t rnorm_bytes = rnorm ? sizeof(CkptRnorm) + sizeof(float) * n : 0;
+  std::vector<char> buf(sizeof h + sizeof ext + nets.size() + ckpt_offset(c, nullptr) + scene_bytes + rnorm_bytes);
   char* q = buf.data();
   memcpy(q, &h, sizeof h); q += sizeof h;
   memcpy(q, &ext, sizeof ext); q += sizeof ext;
@@ -2855,6 +3076,14 @@ int wk_checkpoint_save(wk_ctx* c, const char* path) {
   if (np > 0) {
     memcpy(q, c->scene_desc.data(), sizeof(wk_prop) * np); q += sizeof(wk_prop) * np;
     HIPCHK(c, hipMemcpy(q, c->props, sizeof(float) * n * c->scene.pstride, hipMemcpyDeviceToHost));
+    q += sizeof(float) * n * c->scene.pstride;
+  }
+  if (rnorm) {
+    wk::RnormRec r;
+    HIPCHK(c, hipMemcpy(&r, c->rn_rec, sizeof r, hipMemcpyDeviceToHost));
+    const CkptRnorm s{c->rn_on, c->rn_frozen, c->rn_clip, c->rn_eps, r.count, r.mean, r.m2, r.scale, 0};
+    memcpy(q, &s, sizeof s); q += sizeof s;
+    HIPCHK(c, hipMemcpy(q, c->rn_acc, sizeof(float) * n, hipMemcpyDeviceToHost));
   }
   if (!write_file(path, buf.data(), buf.size())) { SETERR(c, "cannot write checkpoint '%s'", path); return WK_ERR_ARG; }
   return WK_OK;
@@ -2872,7 +3101,7 @@ int wk_checkpoint_load(wk_ctx* c, const char* path) {
   CkptHeader h;
   if (data.size() < sizeof h) { SETERR(c, "checkpoint '%s' truncated", path); return WK_ERR_ARG; }
   memcpy(&h, data.data(), sizeof h);
-  if (h.magic != kCkptMagic || h.version < 2 || h.version > kCkptVersionLogStd) {
+  if (h.magic != kCkptMagic || h.version < 2 || h.version > kCkptVersionRnorm) {
     SETERR(c, "'%s' is not a wk checkpoint", path);
     return WK_ERR_ARG;
   }
@@ -2890,8 +3119,18 @@ int wk_checkpoint_load(wk_ctx* c, const char* path) {
   if (data.size() >= sizeof h + ext_bytes) memcpy(&ext, data.data() + sizeof h, sizeof ext);
   // the networks first: a file of other networks (or of the other kind of kernels) has another
   // parameter count and layout
-  const bool file_learn = h.version >= kCkptVersionLogStd;
-  const bool file_general = file_learn ? ext.reserved0 != 0 : h.version >= kCkptVersionNet;
+  const bool file_rnorm = h.version >= kCkptVersionRnorm;
+  if (file_rnorm != (c->rn_on != 0)) {
+    if (file_rnorm)
+      SETERR(c, "checkpoint '%s' is version %u, written with reward normalisation enabled: enable it on "
+                "this context first (wk_reward_norm_config)", path, h.version);
+    else
+      SETERR(c, "checkpoint '%s' is version %u: a context with reward normalisation enabled loads only "
+                "version %u files", path, h.version, kCkptVersionRnorm);
+    return WK_ERR_ARG;
+  }
+  const bool file_learn = file_rnorm ? ext.reserved1 != 0 : h.version >= kCkptVersionLogStd;
+  const bool file_general = file_learn || file_rnorm ? ext.reserved0 != 0 : h.version >= kCkptVersionNet;
   if (file_learn != (c->cfg.LearnLogStd == 1) || (ext.reserved1 != 0) != file_learn) {
     SETERR(c, "checkpoint '%s' was written with LearnLogStd %d (context: %d)", path, file_learn ? 1 : 0,
            c->cfg.LearnLogStd);
@@ -2943,7 +3182,9 @@ int wk_checkpoint_load(wk_ctx* c, const char* path) {
       need += sizeof(float) * n * pstride;
     }
   }
-  if (h.n_env != n || h.nstate != (uint32_t)wk::NSTATE || h.nparam != (uint32_t)c->np || data.size() != need) {
+  const size_t rnorm_bytes = file_rnorm ? sizeof(CkptRnorm) + sizeof(float) * n : 0;
+  if (h.n_env != n || h.nstate != (uint32_t)wk::NSTATE || h.nparam != (uint32_t)c->np ||
+      data.size() != need + rnorm_bytes) {
     SETERR(c, "checkpoint '%s' is for %u walkers (context has %zu)", path, h.n_env, n);
     return WK_ERR_ARG;
   }
@@ -2958,6 +3199,16 @@ int wk_checkpoint_load(wk_ctx* c, const char* path) {
               "(context: %d / %d / %d)", path, h.iterations, h.max_timesteps, ext.rough_floor,
            c->cfg.Iterations, c->cfg.MaxTimesteps, c->cfg.RoughFloor);
     return WK_ERR_CONFIG;
+  }
+  CkptRnorm rn{};
+  if (file_rnorm) {  // checked like wk_reward_norm_config's and wk_reward_norm_set's arguments
+    memcpy(&rn, data.data() + need, sizeof rn);
+    if (rn.enable != 1 || rn.frozen < 0 || rn.frozen > 1 || !(rn.clip > 0.0f) || !std::isfinite(rn.epsilon) ||
+        rn.epsilon < 0.0f || rn.count < 0 || !std::isfinite(rn.mean) || !std::isfinite(rn.m2) || rn.m2 < 0.0 ||
+        !std::isfinite(rn.scale) || !(rn.scale > 0.0f)) {
+      SETERR(c, "checkpoint '%s': invalid reward-normalisation section", path);
+      return WK_ERR_ARG;
+    }
   }
   if (np > 0 && c->cfg.LanesPerWalker > 1) {  // wk_set_scene would refuse it
     SETERR(c, "checkpoint '%s' has scene props, which need the one-lane mapping "
@@ -2992,6 +3243,15 @@ int wk_checkpoint_load(wk_ctx* c, const char* path) {
   if (file_learn) {
     apply_log_std(c, ls.log_std);
     c->ls_m = ls.m; c->ls_v = ls.v; c->ls_t = ls.t;
+  }
+  if (file_rnorm) {  // the arguments, the statistics with their scale, the walkers' running returns
+    wk::RnormRec r{};
+    r.count = rn.count; r.mean = rn.mean; r.m2 = rn.m2;
+    r.var = rn.count > 0 ? rn.m2 / (double)rn.count : 0.0;
+    r.scale = rn.scale;
+    HIPCHK(c, hipMemcpy(c->rn_rec, &r, sizeof r, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->rn_acc, data.data() + need + sizeof rn, sizeof(float) * n, hipMemcpyHostToDevice));
+    c->rn_frozen = rn.frozen; c->rn_clip = rn.clip; c->rn_eps = rn.epsilon;
   }
   c->rollout_steps = h.rollout_steps;
   c->T_valid = 0;

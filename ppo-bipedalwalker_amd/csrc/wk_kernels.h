@@ -230,6 +230,31 @@ hipError_t launch_returns_std(int n, int T, int use_gae, float gamma, float lamb
                               float* adv, hipStream_t s);
 hipError_t launch_xavier(float* W, uint64_t seed, hipStream_t s);
 
+// Reward normalisation (wk_reward_norm_*; wk_rnorm.hip): rewards scaled by the running standard
+// deviation of the walkers' discounted returns, into a second reward buffer that only the returns
+// kernels read.  RnormRec is the device record; layout == wk_reward_norm (include/wk_api.h), the
+// configuration fields (clip, epsilon, enabled, frozen) filled by the host when it is read.
+struct RnormRec {
+  long long count;
+  double mean, m2, var;
+  float scale, clip, epsilon;
+  int32_t enabled, frozen, pad;
+  long long rows, clipped, nonfinite;
+};
+static_assert(sizeof(RnormRec) == 80, "RnormRec is wk_reward_norm");
+// the scan's tile: RNORM_TILE walkers, one lane each, fold to one partial of RNORM_FIELDS 64-bit
+// words (samples, non-finite samples as integers; sum x, sum x^2 as doubles).  The association is
+// a function of n alone: a tree over the tile's lanes, then the tiles in tile order.
+enum : int { RNORM_TILE = 256, RNORM_FIELDS = 4 };
+int rnorm_tiles(int n);
+// the full pass: scan (acc carried, partial[rnorm_tiles(n)][RNORM_FIELDS]), finish (the merge into
+// rec and the new scale), apply (out = clamp(r * rec->scale)).  learn = false: finish only clears
+// the last pass's counters and the scan does not run -- the apply step with the scale as it is.
+hipError_t launch_rnorm_pass(int n, int T, float gamma, float clip, float epsilon, bool learn,
+                             const float* r, const uint8_t* done, float* acc,
+                             unsigned long long* partial, RnormRec* rec, float* out, hipStream_t s);
+hipError_t launch_rnorm_reset(int n, const uint8_t* mask, float* acc, hipStream_t s);
+
 // the general networks' kernels (wk_net.hip; NetworkKernels = 1).  nets: device copy of
 // {critic, actor}; act_rows: net_act_rows of the two
 enum : int { NET_MAX_BLOCKS = 1024 };  // gradient blocks (one slab each) per minibatch

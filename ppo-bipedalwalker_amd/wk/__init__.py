@@ -50,6 +50,8 @@ EXPORTS = [
     "wk_policy_stats", "wk_update_stats_get", "wk_evaluate", "wk_evaluate_time",
     "wk_grad_norms_get", "wk_set_learning_rate", "wk_get_learning_rate",
     "wk_get_log_std", "wk_set_log_std", "wk_set_log_std_adam", "wk_log_std_gradient",
+    "wk_reward_norm_defaults", "wk_reward_norm_config", "wk_reward_norm_get", "wk_reward_norm_set",
+    "wk_reward_norm_get_acc", "wk_reward_norm_set_acc", "wk_reward_norm_update", "wk_get_scaled_rewards",
 ]
 
 
@@ -215,6 +217,26 @@ class LogStdState(C.Structure):
                 ("m", C.c_double), ("v", C.c_double), ("entropy", C.c_double),
                 ("grad_last", C.c_double), ("steps", C.c_int64), ("clamped", C.c_int64),
                 ("nonfinite", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
+class RewardNormArgs(C.Structure):
+    """wk_reward_norm_args: the switch and the two constants of the reward normalisation"""
+    _fields_ = [("enable", C.c_int32), ("frozen", C.c_int32), ("clip", C.c_float), ("epsilon", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class RewardNorm(C.Structure):
+    """wk_reward_norm: the running statistics of the walkers' discounted returns, the scale the
+    last pass used and that pass's counters (wk_reward_norm_get)"""
+    _fields_ = [("count", C.c_int64), ("mean", C.c_double), ("m2", C.c_double), ("var", C.c_double),
+                ("scale", C.c_float), ("clip", C.c_float), ("epsilon", C.c_float),
+                ("enabled", C.c_int32), ("frozen", C.c_int32), ("pad", C.c_int32),
+                ("rows", C.c_int64), ("clipped", C.c_int64), ("nonfinite", C.c_int64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
@@ -396,6 +418,14 @@ def load_library(path=None):
         "wk_set_log_std": (I, [P, F]),
         "wk_set_log_std_adam": (I, [P, C.c_double, C.c_double, I]),
         "wk_log_std_gradient": (I, [P, C.POINTER(LogStdGrad)]),
+        "wk_reward_norm_defaults": (None, [C.POINTER(RewardNormArgs)]),
+        "wk_reward_norm_config": (I, [P, C.POINTER(RewardNormArgs)]),
+        "wk_reward_norm_get": (I, [P, C.POINTER(RewardNorm)]),
+        "wk_reward_norm_set": (I, [P, C.c_int64, C.c_double, C.c_double]),
+        "wk_reward_norm_get_acc": (I, [P, P]),
+        "wk_reward_norm_set_acc": (I, [P, P]),
+        "wk_reward_norm_update": (I, [P]),
+        "wk_get_scaled_rewards": (I, [P, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -545,6 +575,7 @@ class Engine:
         nc, na = C.c_int(), C.c_int()
         self._chk(self.lib.wk_num_params(self.h, C.byref(nc), C.byref(na)), "wk_num_params")
         self.nparam_critic, self.nparam = nc.value, nc.value + na.value
+        self._t_valid = 0  # rows of the trajectory buffer (scaled_rewards)
 
     # -- plumbing --
     def _chk(self, rc, what):
@@ -697,6 +728,7 @@ class Engine:
 
     def checkpoint_load(self, path):
         self._chk(self.lib.wk_checkpoint_load(self.h, os.fsencode(path)), "wk_checkpoint_load")
+        self._t_valid = 0  # (loading invalidates the trajectory buffer)
 
     # -- data collection (ConsoleRenderer.AddTotalEpisodeReward / AddCriticLoss / AddActorLoss) --
     def collect_data(self, on=True):
@@ -748,6 +780,7 @@ class Engine:
     # -- rollout / PPO --
     def rollout(self, horizon=0):
         self._chk(self.lib.wk_rollout(self.h, int(horizon)), "wk_rollout")
+        self._t_valid = int(horizon) if horizon > 0 else int(self.cfg.Horizon)
 
     def rollout_stats(self):
         s = RolloutStats()
@@ -777,6 +810,7 @@ class Engine:
                 np.ascontiguousarray(dones, np.uint8), _f32(values)]
         self._chk(self.lib.wk_set_trajectory(self.h, int(T), *[_ptr(a) for a in args]),
                   "wk_set_trajectory")
+        self._t_valid = int(T)
 
     def compute_returns(self):
         self._chk(self.lib.wk_compute_returns(self.h), "wk_compute_returns")
@@ -856,6 +890,47 @@ class Engine:
         g = LogStdGrad()
         self._chk(self.lib.wk_log_std_gradient(self.h, C.byref(g)), "wk_log_std_gradient")
         return g.as_dict()
+
+    def reward_norm(self, enable=True, clip=10.0, epsilon=1e-8, frozen=False):
+        """wk_reward_norm_config: scale the rewards the returns kernels read by the running std of
+        the walkers' discounted returns (clamped to +-clip; epsilon is added to the variance).
+        frozen: scale with the statistics as they are.  The raw rewards stay what they are."""
+        a = RewardNormArgs(int(enable), int(frozen), float(clip), float(epsilon))
+        self._chk(self.lib.wk_reward_norm_config(self.h, C.byref(a)), "wk_reward_norm_config")
+
+    def reward_norm_state(self):
+        """wk_reward_norm_get: count, mean, m2, var, scale, the arguments and the last pass's
+        counters (zeros and scale 1 on a context never enabled)"""
+        s = RewardNorm()
+        self._chk(self.lib.wk_reward_norm_get(self.h, C.byref(s)), "wk_reward_norm_get")
+        return s.as_dict()
+
+    def set_reward_norm_state(self, count, mean, m2):
+        """wk_reward_norm_set: replace the running statistics; the scale follows"""
+        self._chk(self.lib.wk_reward_norm_set(self.h, int(count), float(mean), float(m2)), "wk_reward_norm_set")
+
+    def reward_acc(self):
+        """wk_reward_norm_get_acc: every walker's running discounted return"""
+        a = np.empty(self.n, np.float32)
+        self._chk(self.lib.wk_reward_norm_get_acc(self.h, _ptr(a)), "wk_reward_norm_get_acc")
+        return a
+
+    def set_reward_acc(self, a):
+        a = _f32(a, (self.n,))
+        self._chk(self.lib.wk_reward_norm_set_acc(self.h, _ptr(a)), "wk_reward_norm_set_acc")
+
+    def reward_norm_update(self):
+        """wk_reward_norm_update: the full pass (scan, merge, apply) on the current trajectory
+        buffer -- after set_trajectory, whose data is otherwise scaled but not learned"""
+        self._chk(self.lib.wk_reward_norm_update(self.h), "wk_reward_norm_update")
+
+    def scaled_rewards(self, horizon=None):
+        """wk_get_scaled_rewards: the [T][n] rewards the returns kernels read, T the rows of the
+        last rollout / set_trajectory of this object (or `horizon`)"""
+        T = self._t_valid if horizon is None else int(horizon)
+        out = np.empty((T, self.n), np.float32)
+        self._chk(self.lib.wk_get_scaled_rewards(self.h, _ptr(out)), "wk_get_scaled_rewards")
+        return out
 
     def evaluate(self, episodes=1, stochastic=False, start="reset", max_steps=0, poll=0, rng_step0=0,
                  records=False):
