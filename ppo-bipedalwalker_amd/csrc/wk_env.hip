@@ -85,7 +85,7 @@ __global__ void k_returns(int n, int T, int use_gae, float gamma, float lambda,
   }
 }
 
-// host-side launch shims (C++ linkage, used by wk_api.cpp)
+// host-side launch shims (C++ linkage, used by wk_api_env.cpp)
 hipError_t launch_env_scene(int mode, const EnvParams& P, const StepArgs& A, const SceneDev& S,
                             hipStream_t s) {
   if (mode <= 1) (P.rough ? launch_env_scene_given_rough : launch_env_scene_given)(mode, P, A, S, s);

@@ -1,8 +1,8 @@
 // wk_eval.hip -- policy evaluation (wk_evaluate): per-walker episode accounting and the ordered
 // fold of the episode records.
 //
-// The evaluation steps a private copy of the walkers with the kernels the rollout uses (wk_api.cpp
-// wk_evaluate: observations, policy kernel, one env-step of the physics kernel in its
+// The evaluation steps a private copy of the walkers with the kernels the rollout uses
+// (wk_api_eval.cpp wk_evaluate: observations, policy kernel, one env-step of the physics kernel in its
 // caller-actions mode).  After every env-step
 //   k_eval_step    one lane per walker on SoA state (double reward sum, length, best x, episode
 //                  index): adds the step; on `done` writes the slot's record with plain stores
@@ -16,7 +16,7 @@
 //                  stores the block's word;
 //   k_eval_finish  one block: thread f folds field f of the blocks' records in block order.
 // Integers and doubles only, no floating-point atomics: the same records give the same bytes.
-// The host divides (wk_api.cpp).
+// The host divides (wk_api_eval.cpp).
 // Traffic of k_eval_step per walker-step: 13 B of the physics row (reward, done, position x) and
 // 32 B of running state read and written back -- about 45 B, next to a physics launch that moves the
 // 448-B walker record both ways.

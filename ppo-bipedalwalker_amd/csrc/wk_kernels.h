@@ -1,5 +1,5 @@
 // wk_kernels.h -- kernel argument blocks and host launch shims shared by
-// the rollout units (wk_env*.hip), wk_ppo.hip and wk_api.cpp.
+// the rollout units (wk_env*.hip), wk_ppo.hip and the host units (wk_api*.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -17,7 +17,7 @@
 // from 48.9 to 44.2 ms.  Every walker's arithmetic is unchanged (its Philox stream, record and
 // trajectory rows are keyed by its walker id; the policy's matrix-core sums run per walker), so
 // the results are bit-identical to the identity order (tests/test_gpu_order.py).  Not used for
-// the quad mapping on the rough floor (wk_api.cpp launch_physics: there the launch is as long as
+// the quad mapping on the rough floor (wk_api_env.cpp launch_physics: there the launch is as long as
 // its slowest wave, and gathering the few long-lived episode-0 walkers into one wave made it the
 // slowest).
 //

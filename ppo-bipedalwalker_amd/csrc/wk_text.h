@@ -31,7 +31,8 @@ bool json_parse(const std::string& text, JsonValue& out, std::string& why);
 // backslash, control characters, HTML-sensitive <>&'+` and all non-ASCII as \uXXXX.
 std::string json_escape(const std::string& utf8);
 
-// the thread's context-free error text (wk_last_error(NULL)); defined in wk_api.cpp
+// the thread's context-free error text (wk_last_error(NULL)); defined in wk_api.cpp, and the
+// way every other unit sets it
 void set_last_error(const std::string& msg);
 
 }  // namespace wk

@@ -1,5 +1,5 @@
 """GPU: the general networks' kernels (NetworkKernels = 1, csrc/wk_net.hip) and their host loop
-(net_sampled, csrc/wk_api.cpp) where tests/test_gpu_net.py does not reach:
+(net_sampled, csrc/wk_api_env.cpp) where tests/test_gpu_net.py does not reach:
 
   * widths next to the tile edges (netref.NETS edge16 .. edge128: 15 / 16 / 17, 31 / 32 / 33,
     63 / 64 / 65, 127 / 128 against `out` per 16 and `in` per 4, 16 and 32), widths 1 to 3

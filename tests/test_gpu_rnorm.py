@@ -372,6 +372,24 @@ def test_snapshot_and_checkpoint(wk, tmp_path):
         e.close()
 
 
+def test_snapshot_before_the_first_enable(wk):
+    """a snapshot taken before reward normalisation is first enabled holds none of its state: the
+    restore succeeds, puts the walkers back and leaves the record and the running returns alone"""
+    n, T = 5, 4
+    eng = wk.Engine(n, seed=SEED, Horizon=T)
+    eng.snapshot()
+    st0 = eng.get_state()
+    eng.reward_norm(clip=CLIP)
+    eng.rollout()
+    s1, a1 = eng.reward_norm_state(), eng.reward_acc()
+    assert s1["count"] == n * T and a1.any() and eng.get_state().tobytes() != st0.tobytes()
+    eng.restore()
+    assert eng.get_state().tobytes() == st0.tobytes()
+    assert eng.reward_norm_state() == s1 and _rec_bytes(eng.reward_norm_state()) == _rec_bytes(s1)
+    assert eng.reward_acc().tobytes() == a1.tobytes()
+    eng.close()
+
+
 def test_refusals(wk):
     n, T = 5, 4
     on, off, comm = (wk.Engine(n, seed=SEED, Horizon=T) for _ in range(3))
