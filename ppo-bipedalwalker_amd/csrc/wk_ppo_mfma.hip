@@ -187,9 +187,20 @@ void k_ppo_grad_mfma(GradArgs ga) {
     if (c + nw < nchunks) nxt = gather(c + nw);
     const bool valid = c * 16 + n < ga.samples;
     const float act = cur.act, lpo = cur.lpo, ret = cur.ret, adv = cur.adv;
+    // The skip rule first (Matrix.HadamardDivision throws on exp(logp_old) == 0 -> the reference
+    // skips the sample before it touches it).  A row that is not used -- skipped, or past the
+    // minibatch's end -- enters the chunk with zero states: its loss terms are selected zeros
+    // below, but they multiply the row's activations, and 0 * (a non-finite one) would be NaN.
+    // (sv of lane group 3 is the bias column {1, 0, 0, 0}, zeroed with the rest: only the db1 /
+    // dbc1 products read it, against the row's zero gz1 / gzc1; the forward pass adds ba1 itself.)
+    const float eo = expf(lpo);
+    float zd = eo == 0.0f ? 1.0f : 0.0f;
+    zd = rows_max4(zd);
+    const bool use = valid && zd == 0.0f;
+    const f4 sv = use ? cur.sv : z4;
     {
       const int h = (n >> 1) << 1;
-      const f4 v = (h & 2) ? f4{cur.sv[2], cur.sv[3], cur.sv[0], cur.sv[1]} : cur.sv;
+      const f4 v = (h & 2) ? f4{sv[2], sv[3], sv[0], sv[1]} : sv;
       *(f4*)(cb + C_SX + n * 16 + ((4 * g) ^ (h & 12))) = v;
     }
     wave_sync();
@@ -277,10 +288,6 @@ void k_ppo_grad_mfma(GradArgs ga) {
     const float partC = (rr >= ga.lower && rr <= ga.upper) ? 1.0f : 0.0f;
     float l = partA + (partB * partC);
     l = l * -1.0f;
-    const float eo = expf(lpo);
-    float zd = eo == 0.0f ? 1.0f : 0.0f;  // Matrix.HadamardDivision throws -> sample skipped
-    zd = rows_max4(zd);
-    const bool use = valid && zd == 0.0f;
     const float lcd = l / eo;
     const float prob = expf(lp);
     const float frac = (act - mean) / (ga.std_ * ga.std_);
@@ -614,7 +621,13 @@ __global__ __launch_bounds__(64 * 2 * ws::PAIRS) void k_ppo_grad_ws(GradArgs ga)
         const Smp cur = nxt;
         if (i + 1 < kp) nxt = gather(c + nw);
         const bool valid = c * 16 + n < ga.samples;
-        *(f4*)(tb + O_SX + n * RSX + 4 * g) = cur.sv;
+        // the skip rule first: a row that is not used enters with zero states, lane group 3's
+        // bias column included (k_ppo_grad_mfma)
+        const float eo = expf(cur.lpo);
+        float zd = eo == 0.0f ? 1.0f : 0.0f;  // Matrix.HadamardDivision throws -> sample skipped
+        zd = rows_max4(zd);
+        const bool use = valid && zd == 0.0f;
+        *(f4*)(tb + O_SX + n * RSX + 4 * g) = use ? cur.sv : z4;
         wave_sync();
         float sB[3];
 #pragma unroll
@@ -694,10 +707,6 @@ __global__ __launch_bounds__(64 * 2 * ws::PAIRS) void k_ppo_grad_ws(GradArgs ga)
         const float partC = (rr >= ga.lower && rr <= ga.upper) ? 1.0f : 0.0f;
         float l = partA + (partB * partC);
         l = l * -1.0f;
-        const float eo = expf(lpo);
-        float zd = eo == 0.0f ? 1.0f : 0.0f;  // Matrix.HadamardDivision throws -> sample skipped
-        zd = rows_max4(zd);
-        const bool use = valid && zd == 0.0f;
         const float lcd = l / eo;
         const float prob = expf(lp);
         const float frac = (act - mean) / (ga.std_ * ga.std_);
@@ -1014,18 +1023,26 @@ __global__ __launch_bounds__(256 * TEAMS) void k_ppo_grad_tp(GradArgs ga) {
     const Smp cur = nxt;
     if (i + 1 < kp) nxt = gather(c + nt);
     const bool valid = c * 16 + n < ga.samples;
+    // the skip rule first: a row that is not used enters with zero states (k_ppo_grad_mfma)
+    const float eo = expf(cur.lpo);
+    float zd = eo == 0.0f ? 1.0f : 0.0f;  // Matrix.HadamardDivision throws -> sample skipped
+    zd = rows_max4(zd);
+    const bool use = valid && zd == 0.0f;
     f4 h1 = z4, hc1 = z4;
     if (live) {
+      float s[3];
+#pragma unroll
+      for (int t = 0; t < 3; t++) s[t] = use ? cur.s[t] : 0.0f;
       if (w == 0) {
 #pragma unroll
-        for (int t = 0; t < 3; t++) tb[O_SX + n * RSX + 4 * t + g] = cur.s[t];
+        for (int t = 0; t < 3; t++) tb[O_SX + n * RSX + 4 * t + g] = s[t];
       }
       // ---- layer 1 of tile w ----
       f4 z1 = z4, zc1 = z4;
 #pragma unroll
       for (int t = 0; t < 3; t++) {
-        z1 = mfma(wa1[t], cur.s[t], z1);
-        zc1 = mfma(wc1[t], cur.s[t], zc1);
+        z1 = mfma(wa1[t], s[t], z1);
+        zc1 = mfma(wc1[t], s[t], zc1);
       }
 #pragma unroll
       for (int r = 0; r < 4; r++) {
@@ -1087,10 +1104,6 @@ __global__ __launch_bounds__(256 * TEAMS) void k_ppo_grad_tp(GradArgs ga) {
       const float partC = (rr >= ga.lower && rr <= ga.upper) ? 1.0f : 0.0f;
       float l = partA + (partB * partC);
       l = l * -1.0f;
-      const float eo = expf(lpo);
-      float zd = eo == 0.0f ? 1.0f : 0.0f;  // Matrix.HadamardDivision throws -> sample skipped
-      zd = rows_max4(zd);
-      const bool use = valid && zd == 0.0f;
       const float lcd = l / eo;
       const float prob = expf(lp);
       const float frac = (act - mean) / (ga.std_ * ga.std_);

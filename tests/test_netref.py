@@ -172,3 +172,110 @@ def test_surrogate_batch_populates_the_six_cells(name):
         c, a = netref.NETS[name]
         g64 = netref.train_batch_grad64(c, a, w, *batch, len(G))[0]
         np.testing.assert_allclose(g64[-4:], loss_sum, rtol=1e-12, atol=0)
+
+
+# ---- the inputs of tests/test_gpu_grad_edges.py (the built-in matrix-core kernels) ----
+# sha256 over the bytes of (weights, S, A, L, G, Ad) of the B = 96 draws, taken from surrogate_draw
+# as it was before it took keywords (fixed B = 96, log-std -1, RHO)
+B96_SHA256 = {
+    "odd": "1b8b56b13459013dd07ff5ec557ad2483bfd514069ec49d9091ad1c6fc9da2e8",
+    "default": "4e332a8135d94a4eb3cd04ee39f99f32318f814a392308101f3b1fd1c0793bb3",
+}
+
+
+def test_generalised_surrogate_draw_keeps_the_b96_batch():
+    """the keywords' defaults reproduce the B = 96 draws byte for byte (actions and logp_old pass
+    through a float64 forward pass on their way to fp32: a BLAS whose float64 sums differ in the
+    last bit moves an fp32 rounding with a probability near 1e-8 per entry)"""
+    import hashlib
+    assert set(B96_SHA256) == set(net_cases.SURROGATE_CASES)
+    for name, seed in net_cases.SURROGATE_CASES.items():
+        w, batch = net_cases.surrogate_draw(name, seed)
+        assert len(batch[3]) == net_cases.SURROGATE_B == 96
+        h = hashlib.sha256()
+        for x in (w, *batch):
+            h.update(x.tobytes())
+        assert h.hexdigest() == B96_SHA256[name], name
+
+
+def test_grad_edge_table_is_complete():
+    want = {(B, "default") for B in net_cases.GRAD_EDGE_BS} | {(B, "tight") for B in net_cases.TIGHT_BS}
+    assert set(net_cases.GRAD_EDGE_CASES) == want and len(want) == 17
+
+
+@pytest.mark.parametrize("B,variant", sorted(net_cases.GRAD_EDGE_CASES))
+def test_grad_edge_case_meets_its_conditions(B, variant):
+    """the seed is one of the five candidates 2000 + B, + 100, ..., no sample is skipped, the fp32
+    restatement stays within half the bar, the ratios keep clear of the clip edges (fp32 and
+    float64 on the same side) and, from B = 96 and on every non-default case, each of the six cells
+    sign(Adv) x {r < 1 - eps, inside, r > 1 + eps} holds at least B // 12 entries (the cycle gives
+    B / 2, B and B / 2 per sign)"""
+    seed = net_cases.GRAD_EDGE_CASES[(B, variant)]
+    k, rem = divmod(seed - (2000 + B), 100)
+    assert rem == 0 and 0 <= k < net_cases.MAX_SEEDS
+    _, ref_kw = net_cases.grad_edge_params(variant)
+    w, batch = net_cases.grad_edge_case(B, variant)
+    assert len(batch[3]) == B and not (np.exp(batch[2]) == 0).any()
+    ratio = net_cases.restatement_ratio("default", w, batch, **ref_kw)
+    r, counts, _ = net_cases.surrogate_cells("default", w, batch, **ref_kw)
+    print(f"B {B:6d} {variant:8s} seed {seed:6d}  fp32 restatement / bound = {ratio:.3f}  cells {counts.tolist()}")
+    assert ratio <= net_cases.HALF, (B, variant, seed, ratio)
+    eps = ref_kw.get("eps_clip", 0.3)
+    for edge in (1.0 - eps, 1.0 + eps):
+        assert (np.abs(r - edge) >= 1e-3 * edge).all()
+    assert counts.sum() == 4 * B
+    if B >= 96 or variant != "default":
+        assert (counts >= B // 12).all(), counts
+    assert (np.abs(batch[4]) >= 0.1).all()
+
+
+def test_ref64_equals_netref_on_the_surrogate_batch():
+    w, batch = net_cases.surrogate_case("default")
+    a = netref.train_batch_grad64(CD, AD, w, *batch, 96)
+    b = ref64.train_batch_grad64(w, *batch, 96)
+    assert np.abs(a[0] - b[0]).max() <= 1e-12 * np.abs(b[0]).max()
+    assert np.abs(a[1] - b[1]).max() <= 1e-12 * np.abs(b[1]).max()
+    assert a[2] == pytest.approx(b[2], rel=1e-12) and a[3] == pytest.approx(b[3], rel=1e-12) and a[4] == b[4] == 0
+    kw = dict(log_std=-0.5, eps_clip=0.1)
+    w, batch = net_cases.grad_edge_case(96, "tight")
+    a = netref.train_batch_grad64(CD, AD, w, *batch, 96, **kw)
+    b = ref64.train_batch_grad64(w, *batch, 96, **kw)
+    assert np.abs(a[0] - b[0]).max() <= 1e-12 * np.abs(b[0]).max()
+
+
+def test_sweep_positions():
+    B, P = net_cases.SWEEP_B, net_cases.SWEEP_POSITIONS
+    assert B == 16 * 1024 + 7 and len(set(P)) == len(P) == 27 and max(P) == B - 1
+    assert set(range(16)) <= set(P) and {16, 32, 48, 64} <= set(P)
+    for units in (256, 512, 1024):  # tp<1>, tp<2>, ws / mfma: last unit of a pass, first of the next
+        assert 16 * (units - 1) in P and 16 * units in P
+    w, batch = net_cases.surrogate_draw("default", net_cases.SWEEP_SEED, B=B)
+    one = tuple(x[:1] for x in batch)  # the live row: a non-zero gradient in both networks
+    g64 = netref.train_batch_grad64(CD, AD, w, *one, B)[0]
+    assert g64[:897].any() and g64[897:].any()
+
+
+@pytest.mark.parametrize("shape", sorted(net_cases.PERM_CASES))
+def test_perm_cases_meet_their_conditions(orc, shape):
+    """every minibatch of the keyed permutation is without repeats (over the whole epoch too), and
+    the float64 gradient of each has non-zero actor and critic entries (so Adam's moments, which the
+    GPU test compares bit for bit, see every minibatch)"""
+    from conftest import SEED
+    n, T, M, E = shape
+    pool, nmb = n * T, (n * T) // M
+    assert nmb >= 1 and nmb * M <= pool
+    w, traj = net_cases.perm_trajectory(shape)
+    ret, adv = np.empty((T, n), F), np.empty((T, n), F)
+    for i in range(n):
+        ret[:, i], adv[:, i] = orc.returns_mc(traj["rewards"][:, i], traj["values"][:, i], traj["dones"][:, i], 0.9)
+    assert (adv > 0).any() and (adv < 0).any()
+    rows = (traj["states"].reshape(pool, 12), traj["actions"].reshape(pool, 4), traj["logp"].reshape(pool, 4),
+            ret.reshape(pool), adv.reshape(pool))
+    for e in range(E):
+        idx_all = orc.perm_batch(nmb * M, pool, orc.perm_key(SEED, net_cases.PERM_UPDATE, e))
+        assert len(np.unique(idx_all)) == len(idx_all) and idx_all.max() < pool
+        assert not np.array_equal(idx_all, np.arange(len(idx_all)))
+        for j in range(nmb):
+            idx = idx_all[j * M:(j + 1) * M]
+            g64, _, _, _, sk = ref64.train_batch_grad64(w, *(x[idx] for x in rows), M)
+            assert sk == 0 and g64[:897].any() and g64[897:].any()
