@@ -378,7 +378,10 @@ __global__ __launch_bounds__(64) void k_net_grad(NetGradArgs A) {
     __syncthreads();
     net_backward(critic, ga.W, act, g0, g1, slab, first, lane);
 
-    // ---- actor: mean, the per-dimension clipped-surrogate derivative (:248-326), backward ----
+    // ---- actor: mean, the per-dimension clipped-surrogate derivative (:248-326), backward.
+    // (ppo_derivative's text, wk_ppo_math.h, kept here: the critic's half is taken in other lanes
+    // above and the skip is selected after the division; called through the function this kernel
+    // compiles to other code -- DESIGN.md "One derivative") ----
     net_forward(actor, ga.W, act, lane);
     {
       const float mean = act[(actor->row_end + d) * LS + s];

@@ -148,7 +148,10 @@ __global__ __launch_bounds__(64 * WPB) void k_ppo_grad(GradArgs g) {
     const float V = __shfl(zo, 4);
     const float z3 = zo;
     const float mean = tanhf(z3);
-    // ---- PPO derivative (PPOAgent.cs:234-326), per dimension ----
+    // ---- PPO derivative (PPOAgent.cs:234-326), per dimension: ppo_derivative's text
+    // (wk_ppo_math.h), kept here because this kernel leaves a skipped sample with `continue`
+    // between the losses and the batch divisor; called through the function it compiles to other
+    // code (DESIGN.md "One derivative") ----
     const float A = smp[21];
     float criticLoss = 2.0f * (V - smp[20]);
     const float act = smp[12 + d], lpo = smp[16 + d];

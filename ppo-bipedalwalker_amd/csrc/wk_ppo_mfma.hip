@@ -31,16 +31,14 @@
 #include "wk_common.h"
 #include "wk_kernels.h"
 #include "wk_mfma_layout.h"
+#include "wk_mfma_tiles.h"
+#include "wk_ppo_math.h"
 
 namespace wk {
 
-#define DEV __device__ __forceinline__
-typedef float f4 __attribute__((ext_vector_type(4)));
-
 namespace mf {
 enum : int {
-  RS = 80,               // row stride of a [16 samples][64] tile
-  C_H1 = 0, C_HC1 = C_H1 + 16 * RS, C_H2 = C_HC1 + 16 * RS, C_G2 = C_H2 + 16 * RS,
+  C_H1 = 0, C_HC1 = C_H1 + 16 * RS, C_H2 = C_HC1 + 16 * RS, C_G2 = C_H2 + 16 * RS,  // [16 samples][RS] tiles
   C_SX = C_G2 + 16 * RS,  // [16][16]: 12 features, 1.0 (bias column), 0, 0, 0
   C_G3 = C_SX + 256,      // [16][16]: gz3 (4 dims), dV, zeros
   CHUNK = C_G3 + 256,
@@ -50,52 +48,6 @@ enum : int {
 };
 static_assert(LDS_FLOATS >= WAVES * SLAB, "the epilogue's per-wave slabs fit");
 }  // namespace mf
-
-// ActivationLayer LeakyReLU(0.2) = Math.Max(0.2 z, z): z for z >= 0 (and -0: Max keeps
-// the equal-valued 0.2 * -0 = -0), 0.2 z below, NaN through.  As v_max_f32(0.2 z, z) it is the
-// same value for every input (0.2 z is NaN exactly when z is, has z's sign, and is the larger
-// one exactly when z < 0): two instructions instead of multiply, compare and select.
-DEV float mf_lrelu(float z) { return __builtin_fmaxf(0.2f * z, z); }
-DEV float mf_dlrelu(float z) { return z < 0.0f ? 0.2f : 1.0f; }
-DEV void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// [16 samples][RS] tile addressing, bank-conflict-free both ways (MI355X_MICROARCH §LDS):
-// column groups of 4 are XOR-swizzled by row bits 1..2.  A lane (n, g) stores an f4 at
-// [row n][cols c..c+3] (ds_write_b128: 8-lane groups, banks mod 32 -> the 8 rows of a group
-// land on 8 distinct 16-B slots); a lane (n, g) reads [row 4t + g][col 16i + n]
-// (ds_read_b32: 32-lane halves; the swizzle is uniform over a half, so RS = 80 keeps the two
-// rows of a half on opposite 16-bank halves).
-DEV int tw(int row, int col4) { return row * mf::RS + (col4 ^ (((row >> 1) & 3) << 2)); }
-DEV int tr(int row, int col) { return row * mf::RS + (col ^ (((row >> 1) & 3) << 2)); }
-// [16][16] tiles (SX, G3): columns XOR-swizzled by 2 (row >> 1), read as [row n][col 4t + g]
-// and [row 4t + g][col n] without conflicts; the f4 store of SX moves its group and swaps
-// its element pairs accordingly
-DEV int sx(int row, int col) { return row * 16 + (col ^ ((row >> 1) << 1)); }
-DEV f4 mfma(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-// sum over the 16 lanes of a DPP row (all lanes get the total)
-DEV float row_sum16(float v) {
-  v = v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));
-  v = v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false));
-  v = v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false));
-  v = v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, false));
-  return v;
-}
-
-// Block slabs of the ordered reduction, written through to memory (sc1 buffer stores): the
-// kernel-end release then has no dirty slab lines to write back out of the L2, and the
-// reduction reads them from other XCDs anyway (tile-parallel kernel 12.9 -> 12.2 us per launch
-// at 8,192 samples, the reduction unchanged).
-struct SlabOut {
-  __amdgpu_buffer_rsrc_t r;
-  DEV explicit SlabOut(float* base) : r(__builtin_amdgcn_make_buffer_rsrc(base, 0, SLAB * 4, 0x00020000)) {}
-  DEV void put(int i, f4 v) const {  // 16-byte element i
-    typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, v), r, i * 16, 0, 16);
-  }
-};
 
 __global__ __launch_bounds__(64 * mf::WAVES) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void k_ppo_grad_mfma(GradArgs ga) {
@@ -107,41 +59,12 @@ void k_ppo_grad_mfma(GradArgs ga) {
   const int nchunks = (ga.samples + 15) / 16;
   const int nw = gridDim.x * WAVES;
   // gather (CreateBatches, PPOAgent.cs:512-533), one chunk ahead of the math
-  struct Smp { f4 sv; float act, lpo, ret, adv; };
-  auto gather = [&](int c) {
-    Smp m;
-    const int pos = c * 16 + n;
-    uint32_t idx = ga.base + (uint32_t)(pos < ga.samples ? pos : 0);
-    if (ga.use_perm) idx = perm_apply(idx, ga.pk);
-    m.sv = f4{1.0f, 0.0f, 0.0f, 0.0f};  // lane group 3: the bias column
-    if (g < 3) m.sv = *(const f4*)(ga.states + (size_t)idx * 12 + 4 * g);
-    m.act = ga.actions[(size_t)idx * 4 + g];
-    m.lpo = ga.logp_old[(size_t)idx * 4 + g];
-    m.ret = ga.returns[idx];
-    m.adv = ga.adv[idx];
-    return m;
-  };
+  auto gather = [&](int c) { return gather_chunk<true, false>(ga, c, n, g); };
   int c = blockIdx.x * WAVES + wave;
   // the first chunk's gather is in flight while the weights are staged
   Smp nxt = gather(c < nchunks ? c : 0);
 
-  // ---- stage the weight image (already in operand order, wk_mfma_layout.h): every
-  // thread's loads are issued before its first LDS write, so the copy costs one L2
-  // round trip instead of one per 4 KB ----
-  {
-    constexpr int NV = WEND / 4, PER = (NV + 64 * WAVES - 1) / (64 * WAVES);
-    f4 wv[PER];
-#pragma unroll
-    for (int i = 0; i < PER; i++) {
-      const int e = tid + i * 64 * WAVES;
-      if (e < NV) wv[i] = ((const f4*)ga.Wz)[e];
-    }
-#pragma unroll
-    for (int i = 0; i < PER; i++) {
-      const int e = tid + i * 64 * WAVES;
-      if (e < NV) ((f4*)lds)[e] = wv[i];
-    }
-  }
+  stage_weights<64 * WAVES>(ga.Wz, lds, tid);
   float* cb = lds + WEND + wave * CHUNK;
   for (int e = lane; e < 256; e += 64) cb[C_G3 + e] = 0.0f;
   __syncthreads();
@@ -187,22 +110,15 @@ void k_ppo_grad_mfma(GradArgs ga) {
     if (c + nw < nchunks) nxt = gather(c + nw);
     const bool valid = c * 16 + n < ga.samples;
     const float act = cur.act, lpo = cur.lpo, ret = cur.ret, adv = cur.adv;
-    // The skip rule first (Matrix.HadamardDivision throws on exp(logp_old) == 0 -> the reference
-    // skips the sample before it touches it).  A row that is not used -- skipped, or past the
+    // The skip rule first (ppo_row_used: Matrix.HadamardDivision throws on exp(logp_old) == 0 -> the
+    // reference skips the sample before it touches it).  A row that is not used -- skipped, or past the
     // minibatch's end -- enters the chunk with zero states: its loss terms are selected zeros
     // below, but they multiply the row's activations, and 0 * (a non-finite one) would be NaN.
     // (sv of lane group 3 is the bias column {1, 0, 0, 0}, zeroed with the rest: only the db1 /
     // dbc1 products read it, against the row's zero gz1 / gzc1; the forward pass adds ba1 itself.)
-    const float eo = expf(lpo);
-    float zd = eo == 0.0f ? 1.0f : 0.0f;
-    zd = rows_max4(zd);
-    const bool use = valid && zd == 0.0f;
-    const f4 sv = use ? cur.sv : z4;
-    {
-      const int h = (n >> 1) << 1;
-      const f4 v = (h & 2) ? f4{sv[2], sv[3], sv[0], sv[1]} : sv;
-      *(f4*)(cb + C_SX + n * 16 + ((4 * g) ^ (h & 12))) = v;
-    }
+    float eo;
+    const bool use = ppo_row_used(valid, lpo, eo);
+    sx_put(cb + C_SX, n, g, use ? cur.sv : z4);
     wave_sync();
 
     // ---- layer 1, actor and critic ----
@@ -273,29 +189,10 @@ void k_ppo_grad_mfma(GradArgs ga) {
     const float z3 = rows_rsum4(p3) + b3g;  // (lane (n, g): dim g)
     const float V = pv + bc2;
 
-    // ---- PPO derivative for action dimension d = g (PPOAgent.cs:234-326) ----
-    const float mean = tanhf(z3);
-    float criticLoss = 2.0f * (V - ret);
-    float fr = (act - mean) / ga.std_;
-    fr *= fr;
-    fr /= 2.0f;
-    const float lp = ga.lp_const - fr;
-    const float rr = expf(lp - lpo);
-    const float cr = rr >= ga.upper ? ga.upper : (rr <= ga.lower ? ga.lower : rr);
-    const float cra = cr * adv, ra = rr * adv;
-    const float partA = (ra <= cra ? 1.0f : 0.0f) * adv;
-    const float partB = (cra < ra ? 1.0f : 0.0f) * adv;
-    const float partC = (rr >= ga.lower && rr <= ga.upper) ? 1.0f : 0.0f;
-    float l = partA + (partB * partC);
-    l = l * -1.0f;
-    const float lcd = l / eo;
-    const float prob = expf(lp);
-    const float frac = (act - mean) / (ga.std_ * ga.std_);
-    float actorLoss = (prob * frac) * lcd;
-    criticLoss = use ? criticLoss / ga.b_div : 0.0f;
-    actorLoss = use ? actorLoss / ga.b_div : 0.0f;
-    const float th = mean;  // tanh(z3) again in the reference's backward pass
-    const float gz3 = actorLoss * (1.0f - (th * th));
+    // ---- PPO derivative for action dimension d = g (wk_ppo_math.h, PPOAgent.cs:234-326) ----
+    const PpoTerms pl = ppo_derivative(use, tanhf(z3), V, act, lpo, eo, ret, adv, ga.std_, ga.lp_const, ga.upper,
+                                       ga.lower, ga.b_div);
+    const float criticLoss = pl.criticLoss, actorLoss = pl.actorLoss, gz3 = pl.gz3;
     float al[4], q[4];
     rows_bcast4(actorLoss, al);
     rows_bcast4(gz3, q);
@@ -416,6 +313,9 @@ void k_ppo_grad_mfma(GradArgs ga) {
   __syncthreads();  // every wave is done with the weights and tiles
   float* slab = lds + wave * SLAB;  // every entry below is written exactly once
   if (lane < SLAB - (NPARAM + 3)) slab[NPARAM + 3 + lane] = 0.0f;  // (the pads)
+  // dW2, dW1 | db1, dWc1 | dbc1 (the same text as k_ppo_grad_ws's consumer, in both on purpose:
+  // handed to a helper, by reference or by value, the accumulator arrays are packed otherwise and
+  // both kernels compile to other code -- DESIGN.md "One derivative")
 #pragma unroll
   for (int Mj = 0; Mj < 4; Mj++)
 #pragma unroll
@@ -454,25 +354,9 @@ void k_ppo_grad_mfma(GradArgs ga) {
     }
   }
   __syncthreads();
-  // the block fold, 16 bytes per lane and step with every LDS read of a lane issued up front
-  // (same element order: ((0 + w0) + w1) + w2) + w3)
+  // the block fold (fold_slabs: ((0 + w0) + w1) + w2) + w3 per element)
   f4* out = (f4*)(ga.partial + (size_t)blockIdx.x * SLAB);
-  constexpr int NV = SLAB / 4, PER = (NV + 64 * WAVES - 1) / (64 * WAVES);
-  f4 sv[PER][WAVES];
-#pragma unroll
-  for (int k = 0; k < PER; k++) {
-    const int i = tid + k * 64 * WAVES;
-#pragma unroll
-    for (int w = 0; w < WAVES; w++) sv[k][w] = i < NV ? ((const f4*)(lds + w * SLAB))[i] : z4;
-  }
-#pragma unroll
-  for (int k = 0; k < PER; k++) {
-    const int i = tid + k * 64 * WAVES;
-    f4 acc = z4;
-#pragma unroll
-    for (int w = 0; w < WAVES; w++) acc = acc + sv[k][w];
-    if (i < NV) out[i] = acc;
-  }
+  fold_slabs<64 * WAVES, WAVES, true>(lds, tid, [&](int i, f4 v) { out[i] = v; });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -520,7 +404,9 @@ __global__ __launch_bounds__(64 * 2 * ws::PAIRS) void k_ppo_grad_ws(GradArgs ga)
   // barriers -- both paths execute the same number.)
   // the weight image into LDS first, by the block's first four waves (the first launched): their
   // loads are in flight while the others launch, and the pairing barrier below publishes the image
-  // with the SIMD ids (one block barrier and one L2 round trip fewer before the first chunk)
+  // with the SIMD ids (one block barrier and one L2 round trip fewer before the first chunk).
+  // (stage_weights<256>'s text, kept here: through the helper this kernel's prologue gains an
+  // instruction and k_ppo_grad_mfma, which shares the instantiation, changes too)
   if (tid < 256) {
     constexpr int NV = WEND / 4, PER = (NV + 256 - 1) / 256;
     f4 wv[PER];
@@ -567,24 +453,8 @@ __global__ __launch_bounds__(64 * 2 * ws::PAIRS) void k_ppo_grad_ws(GradArgs ga)
   const int kp = c0 < nchunks ? (nchunks - 1 - c0) / nw + 1 : 0;         // this pair's chunks
   const int kmax = blockIdx.x * PAIRS < nchunks ? (nchunks - 1 - blockIdx.x * PAIRS) / nw + 1 : 0;
 
-  struct Smp { f4 sv; float act, lpo, ret, adv; };
-  auto gather = [&](int c) {
-    Smp m;
-    const int pos = c * 16 + n;
-    uint32_t idx = ga.base + (uint32_t)(pos < ga.samples ? pos : 0);
-    if (ga.use_perm) idx = perm_apply(idx, ga.pk);
-    // (the lane group through an opaque copy: hoisted, `states + 4 g` was a per-lane 64-bit base
-    // the allocator kept in scratch and reloaded before every chunk's gather)
-    uint32_t go = (uint32_t)g;
-    asm volatile("" : "+v"(go));
-    m.sv = f4{1.0f, 0.0f, 0.0f, 0.0f};  // lane group 3: the bias column
-    if (g < 3) m.sv = *(const f4*)(ga.states + ((size_t)idx * 12 + 4 * go));
-    m.act = ga.actions[(size_t)idx * 4 + go];
-    m.lpo = ga.logp_old[(size_t)idx * 4 + go];
-    m.ret = ga.returns[idx];
-    m.adv = ga.adv[idx];
-    return m;
-  };
+  // (the lane group through gather_chunk's opaque copy)
+  auto gather = [&](int c) { return gather_chunk<true, true>(ga, c, n, g); };
   Smp nxt;
   if (producer) nxt = gather(c0 < nchunks ? c0 : 0);
   float* const pt = lds + WEND + pair * 2 * TB;  // this pair's two tile buffers
@@ -623,10 +493,8 @@ __global__ __launch_bounds__(64 * 2 * ws::PAIRS) void k_ppo_grad_ws(GradArgs ga)
         const bool valid = c * 16 + n < ga.samples;
         // the skip rule first: a row that is not used enters with zero states, lane group 3's
         // bias column included (k_ppo_grad_mfma)
-        const float eo = expf(cur.lpo);
-        float zd = eo == 0.0f ? 1.0f : 0.0f;  // Matrix.HadamardDivision throws -> sample skipped
-        zd = rows_max4(zd);
-        const bool use = valid && zd == 0.0f;
+        float eo;
+        const bool use = ppo_row_used(valid, cur.lpo, eo);
         *(f4*)(tb + O_SX + n * RSX + 4 * g) = use ? cur.sv : z4;
         wave_sync();
         float sB[3];
@@ -691,30 +559,10 @@ __global__ __launch_bounds__(64 * 2 * ws::PAIRS) void k_ppo_grad_ws(GradArgs ga)
         pv = rows_sum4(pv);
         const float z3 = rows_rsum4(p3) + b3g;  // (lane (n, g): dim g)
         const float V = pv + bc2;
-        // ---- PPO derivative for action dimension d = g (PPOAgent.cs:234-326) ----
-        const float act = cur.act, lpo = cur.lpo, ret = cur.ret, adv = cur.adv;
-        const float mean = tanhf(z3);
-        float criticLoss = 2.0f * (V - ret);
-        float fr = (act - mean) / ga.std_;
-        fr *= fr;
-        fr /= 2.0f;
-        const float lp = ga.lp_const - fr;
-        const float rr = expf(lp - lpo);
-        const float cr = rr >= ga.upper ? ga.upper : (rr <= ga.lower ? ga.lower : rr);
-        const float cra = cr * adv, ra = rr * adv;
-        const float partA = (ra <= cra ? 1.0f : 0.0f) * adv;
-        const float partB = (cra < ra ? 1.0f : 0.0f) * adv;
-        const float partC = (rr >= ga.lower && rr <= ga.upper) ? 1.0f : 0.0f;
-        float l = partA + (partB * partC);
-        l = l * -1.0f;
-        const float lcd = l / eo;
-        const float prob = expf(lp);
-        const float frac = (act - mean) / (ga.std_ * ga.std_);
-        float actorLoss = (prob * frac) * lcd;
-        criticLoss = use ? criticLoss / ga.b_div : 0.0f;
-        actorLoss = use ? actorLoss / ga.b_div : 0.0f;
-        const float th = mean;  // tanh(z3) again in the reference's backward pass
-        const float gz3 = actorLoss * (1.0f - (th * th));
+        // ---- PPO derivative for action dimension d = g (wk_ppo_math.h, PPOAgent.cs:234-326) ----
+        const PpoTerms pl = ppo_derivative(use, tanhf(z3), V, cur.act, cur.lpo, eo, cur.ret, cur.adv, ga.std_,
+                                           ga.lp_const, ga.upper, ga.lower, ga.b_div);
+        const float criticLoss = pl.criticLoss, actorLoss = pl.actorLoss, gz3 = pl.gz3;
         float al[4], q[4];
         rows_bcast4(actorLoss, al);
         rows_bcast4(gz3, q);
@@ -871,46 +719,31 @@ __global__ __launch_bounds__(64 * 2 * ws::PAIRS) void k_ppo_grad_ws(GradArgs ga)
       __syncthreads();
     }
     __syncthreads();  // (matches the producer's: weights and tiles are free)
-    float* const slab = lds + pair * SLAB;
+    float* const slab = lds + pair * SLAB;  // (k_ppo_grad_mfma's write-out of the same accumulators)
 #pragma unroll
-    for (int Mj = 0; Mj < 4; Mj++)
+  for (int Mj = 0; Mj < 4; Mj++)
 #pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const int j = 16 * Mj + 4 * g + r;
+    for (int r = 0; r < 4; r++) {
+      const int j = 16 * Mj + 4 * g + r;
 #pragma unroll
-        for (int Nk = 0; Nk < 4; Nk++) slab[OFF_A_W2 + j * 64 + 16 * Nk + n] = a2[Mj][Nk][r];
-        if (n < 12) {
-          slab[OFF_A_W1 + j * 12 + n] = a1[Mj][r];
-          slab[OFF_C_W1 + j * 12 + n] = a1c[Mj][r];
-        } else if (n == 12) {
-          slab[OFF_A_B1 + j] = a1[Mj][r];
-          slab[OFF_C_B1 + j] = a1c[Mj][r];
-        }
+      for (int Nk = 0; Nk < 4; Nk++) slab[OFF_A_W2 + j * 64 + 16 * Nk + n] = a2[Mj][Nk][r];
+      if (n < 12) {
+        slab[OFF_A_W1 + j * 12 + n] = a1[Mj][r];
+        slab[OFF_C_W1 + j * 12 + n] = a1c[Mj][r];
+      } else if (n == 12) {
+        slab[OFF_A_B1 + j] = a1[Mj][r];
+        slab[OFF_C_B1 + j] = a1c[Mj][r];
       }
+    }
   }
   __syncthreads();  // the pair slabs are complete
   // the block fold over the four pair slabs, in pair order
   const SlabOut out(ga.partial + (size_t)blockIdx.x * SLAB);
-  constexpr int NV = SLAB / 4, PER = (NV + 512 - 1) / 512;
   // (the thread index through an opaque copy: otherwise the prologue's 16-byte offset of the
   // weight copy is reused here and kept in scratch across the chunk loop)
   int tf = tid;
   asm volatile("" : "+v"(tf));
-  f4 sv[PER][PAIRS];
-#pragma unroll
-  for (int k = 0; k < PER; k++) {
-    const int i = tf + k * 512;
-#pragma unroll
-    for (int w = 0; w < PAIRS; w++) sv[k][w] = i < NV ? ((const f4*)(lds + w * SLAB))[i] : z4;
-  }
-#pragma unroll
-  for (int k = 0; k < PER; k++) {
-    const int i = tf + k * 512;
-    f4 acc = z4;
-#pragma unroll
-    for (int w = 0; w < PAIRS; w++) acc = acc + sv[k][w];
-    if (i < NV) out.put(i, acc);
-  }
+  fold_slabs<512, PAIRS, true>(lds, tf, [&](int i, f4 v) { out.put(i, v); });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1024,10 +857,8 @@ __global__ __launch_bounds__(256 * TEAMS) void k_ppo_grad_tp(GradArgs ga) {
     if (i + 1 < kp) nxt = gather(c + nt);
     const bool valid = c * 16 + n < ga.samples;
     // the skip rule first: a row that is not used enters with zero states (k_ppo_grad_mfma)
-    const float eo = expf(cur.lpo);
-    float zd = eo == 0.0f ? 1.0f : 0.0f;  // Matrix.HadamardDivision throws -> sample skipped
-    zd = rows_max4(zd);
-    const bool use = valid && zd == 0.0f;
+    float eo;
+    const bool use = ppo_row_used(valid, cur.lpo, eo);
     f4 h1 = z4, hc1 = z4;
     if (live) {
       float s[3];
@@ -1088,30 +919,10 @@ __global__ __launch_bounds__(256 * TEAMS) void k_ppo_grad_tp(GradArgs ga) {
       }
       z3 = z3 + b3g;
       const float V = pv + bc2;
-      // ---- PPO derivative for action dimension d = g (PPOAgent.cs:234-326) ----
-      const float act = cur.act, lpo = cur.lpo, ret = cur.ret, adv = cur.adv;
-      const float mean = tanhf(z3);
-      float criticLoss = 2.0f * (V - ret);
-      float fr = (act - mean) / ga.std_;
-      fr *= fr;
-      fr /= 2.0f;
-      const float lp = ga.lp_const - fr;
-      const float rr = expf(lp - lpo);
-      const float cr = rr >= ga.upper ? ga.upper : (rr <= ga.lower ? ga.lower : rr);
-      const float cra = cr * adv, ra = rr * adv;
-      const float partA = (ra <= cra ? 1.0f : 0.0f) * adv;
-      const float partB = (cra < ra ? 1.0f : 0.0f) * adv;
-      const float partC = (rr >= ga.lower && rr <= ga.upper) ? 1.0f : 0.0f;
-      float l = partA + (partB * partC);
-      l = l * -1.0f;
-      const float lcd = l / eo;
-      const float prob = expf(lp);
-      const float frac = (act - mean) / (ga.std_ * ga.std_);
-      float actorLoss = (prob * frac) * lcd;
-      criticLoss = use ? criticLoss / ga.b_div : 0.0f;
-      actorLoss = use ? actorLoss / ga.b_div : 0.0f;
-      const float th = mean;  // tanh(z3) again in the reference's backward pass
-      const float gz3 = actorLoss * (1.0f - (th * th));
+      // ---- PPO derivative for action dimension d = g (wk_ppo_math.h, PPOAgent.cs:234-326) ----
+      const PpoTerms pl = ppo_derivative(use, tanhf(z3), V, cur.act, cur.lpo, eo, cur.ret, cur.adv, ga.std_,
+                                         ga.lp_const, ga.upper, ga.lower, ga.b_div);
+      const float criticLoss = pl.criticLoss, actorLoss = pl.actorLoss, gz3 = pl.gz3;
       float q[4];
       rows_bcast4(gz3, q);
       if (w == 0) {  // the sample-level terms, once per team
@@ -1237,21 +1048,7 @@ __global__ __launch_bounds__(256 * TEAMS) void k_ppo_grad_tp(GradArgs ga) {
   __syncthreads();
   {
     const SlabOut out(ga.partial + (size_t)blockIdx.x * SLAB);
-    constexpr int NV = SLAB / 4, PER = (NV + 256 * TEAMS - 1) / (256 * TEAMS);
-    f4 sv[PER][TEAMS];
-#pragma unroll
-    for (int k = 0; k < PER; k++) {
-      const int i = tid + k * 256 * TEAMS;
-#pragma unroll
-      for (int t = 0; t < TEAMS; t++) sv[k][t] = i < NV ? ((const f4*)(lds + t * SLAB))[i] : z4;
-    }
-#pragma unroll
-    for (int k = 0; k < PER; k++) {
-      const int i = tid + k * 256 * TEAMS;
-      f4 acc = sv[k][0];
-      if (TEAMS == 2) acc = acc + sv[k][TEAMS - 1];
-      if (i < NV) out.put(i, acc);
-    }
+    fold_slabs<256 * TEAMS, TEAMS, false>(lds, tid, [&](int i, f4 v) { out.put(i, v); });
   }
 }
 

@@ -10,6 +10,7 @@
 
 #include "wk_kernels.h"
 #include "wk_mfma_layout.h"
+#include "wk_ppo_math.h"
 
 namespace wk {
 
@@ -31,32 +32,29 @@ struct StatsAcc : std::conditional<LS, StatsAccLS, StatsAccNone>::type {
 // the larger of the two; a NaN on either side stays
 __device__ __forceinline__ double stats_max(double m, double v) { return (v > m || v != v) ? v : m; }
 
-// One entry, in lane (row n, dim g) of a wave whose 64 lanes are all active: the quantities as
-// the gradient kernels define them (wk_ppo_mfma.hip "PPO derivative", PPOAgent.cs:234-326) --
-// fr, lp, rr and the clip in fp32 -- then d = lp - lpo in fp32 and everything after it in double.
-// valid: the row exists; the skip rule (expf(lpo) == 0 in any of the row's four dimensions)
-// decides with it whether the row counts.  Returns lp (for every row).
-// LS: w = rr (partA + partB partC), the gradient kernels' selection of the clipped surrogate's
-// derivative by lp, in fp32; d lp / d log_std = zz - 1 with zz = ((act - mean) / std)^2, the fr
-// of above before its halving; the entry's term (double)w ((double)zz - 1) and zz in double.
+// One entry, in lane (row n, dim g) of a wave whose 64 lanes are all active: zz, lp, rr and the
+// clipped surrogates are ppo_derivative's (wk_ppo_math.h, the function the gradient kernels call,
+// PPOAgent.cs:234-326) in fp32, then d = lp - lpo in fp32 and everything after it in double.
+// valid: the row exists; the skip rule (ppo_row_used: expf(lpo) == 0 in any of the row's four
+// dimensions) decides with it whether the row counts.  Returns lp (for every row).
+// LS: w = rr sel with ppo_derivative's sel = partA + partB partC, the gradient kernels' selection
+// of the clipped surrogate's derivative by lp, in fp32; d lp / d log_std = zz - 1 with zz =
+// ((act - mean) / std)^2; the entry's term (double)w ((double)zz - 1) and zz in double.
 template <bool LS>
 __device__ __forceinline__ float stats_entry(StatsAcc<LS>& a, const GradArgs& ga, bool valid, bool row_lane,
                                              float mean, float V, float act, float lpo, float ret,
                                              float adv) {
-  float fr = (act - mean) / ga.std_;
-  fr *= fr;
-  const float zz = fr;
-  fr /= 2.0f;
-  const float lp = ga.lp_const - fr;
+  // (the loss members are not read here, so `use` and eo, which only they depend on, are not the
+  // skip rule's: that follows the terms, as it always did in this text)
+  auto terms = [&] {
+    return ppo_derivative(valid, mean, V, act, lpo, 1.0f, ret, adv, ga.std_, ga.lp_const, ga.upper, ga.lower, ga.b_div);
+  };
+  const PpoTerms t = terms();
+  const float zz = t.zz, lp = t.lp, rr = t.rr, cra = t.cra, ra = t.ra;
   const float d = lp - lpo;
-  const float rr = expf(d);
-  const float cr = rr >= ga.upper ? ga.upper : (rr <= ga.lower ? ga.lower : rr);
-  const float cra = cr * adv, ra = rr * adv;
   const float sg = ra <= cra ? ra : cra;
-  const float eo = expf(lpo);
-  float zd = eo == 0.0f ? 1.0f : 0.0f;
-  zd = rows_max4(zd);
-  const bool use = valid && zd == 0.0f;
+  float eo;
+  const bool use = ppo_row_used(valid, lpo, eo);
   if (use) {
     const double dd = (double)d;
     a.kl += expm1(dd) - dd;
@@ -65,10 +63,7 @@ __device__ __forceinline__ float stats_entry(StatsAcc<LS>& a, const GradArgs& ga
     a.clipped += (rr > ga.upper || rr < ga.lower) ? 1 : 0;
     a.rmax = (rr > a.rmax || rr != rr) ? rr : a.rmax;
     if constexpr (LS) {
-      const float partA = (ra <= cra ? 1.0f : 0.0f) * adv;
-      const float partB = (cra < ra ? 1.0f : 0.0f) * adv;
-      const float partC = (rr >= ga.lower && rr <= ga.upper) ? 1.0f : 0.0f;
-      const float w = rr * (partA + (partB * partC));
+      const float w = rr * terms().sel;  // (evaluated here, in the counted branch: the same value as t.sel)
       a.term += (double)w * ((double)zz - 1.0);
       a.zz += (double)zz;
     }

@@ -4,11 +4,15 @@
 // the blocks' records (both kernel families); and k_ppo_logstd, the same pass instantiated with
 // the log-std's derivative (wk_log_std_gradient, the LearnLogStd step).
 //
-// The forward pass is k_ppo_grad_mfma's forward half restated (wk_ppo_mfma.hip: the weight image
-// Wz staged into LDS once per block, one wave per chunk of 16 rows, layer 1 and 2 on
+// The forward pass has k_ppo_grad_mfma's operation order (wk_ppo_mfma.hip), on the helpers the two
+// share (wk_mfma_tiles.h: the weight image Wz staged into LDS once per block by stage_weights, the
+// chunk gather, the SX tile, mfma / mf_lrelu): one wave per chunk of 16 rows, layer 1 and 2 on
 // v_mfma_f32_16x16x4_f32 with layer 1's D registers as layer 2's B operand, the output rows as
-// 64-long dots on the VALU, lane (n, g) ending with z3 of dimension g and V of row n), so a row's
-// mean, log-density and value are the gradient kernel's bit for bit.  The only LDS tile a forward
+// 64-long dots on the VALU, lane (n, g) ending with z3 of dimension g and V of row n, so a row's
+// mean, log-density and value are the gradient kernel's bit for bit.  The layers themselves are
+// written out here a second time: this pass reads biases and output rows from LDS where it uses
+// them and stores no H tiles, the gradient kernel keeps them in registers and stores the tiles
+// (DESIGN.md "One derivative").  The only LDS tile a forward
 // pass needs is SX.  Rows are read in buffer order; the grid is capped (STATS_MAX_BLOCKS) and the
 // waves stride over the chunks, the next chunk's rows in flight during the math.
 //
@@ -18,12 +22,12 @@
 #include "wk_common.h"
 #include "wk_kernels.h"
 #include "wk_mfma_layout.h"
+#include "wk_mfma_tiles.h"
 #include "wk_stats.h"
 
 namespace wk {
 
 #define DEV __device__ __forceinline__
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 namespace st {
 enum : int {
@@ -34,16 +38,6 @@ enum : int {
 static_assert((size_t)LDS_FLOATS * 4 >= (size_t)WAVES * STATS_FIELDS_LS * 64 * 8, "the fold's images fit");
 static_assert(LDS_FLOATS * 4 <= 64 * 1024, "static LDS");
 }  // namespace st
-
-DEV float st_lrelu(float z) { return __builtin_fmaxf(0.2f * z, z); }  // (mf_lrelu)
-DEV void st_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// the [16][16] SX tile's addressing (wk_ppo_mfma.hip sx): columns XOR-swizzled by 2 (row >> 1)
-DEV int st_sx(int row, int col) { return row * 16 + (col ^ ((row >> 1) << 1)); }
-DEV f4 st_mfma(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // (two waves per SIMD: a full grid is two blocks per CU, and the second wave fills the first's
 // MFMA dependency waits; biases and output rows are read from LDS where they are used, so the
@@ -63,37 +57,12 @@ DEV void ppo_stats_pass(const StatsArgs& sa) {
 
   const int nchunks = (ga.samples + 15) / 16;
   const int nw = gridDim.x * WAVES;
-  struct Smp { f4 sv; float act, lpo, ret, adv; };
-  auto gather = [&](int c) {
-    Smp m;
-    const int pos = c * 16 + n;
-    const size_t idx = (size_t)(pos < ga.samples ? pos : 0);
-    m.sv = f4{1.0f, 0.0f, 0.0f, 0.0f};
-    if (g < 3) m.sv = *(const f4*)(ga.states + idx * 12 + 4 * g);
-    m.act = ga.actions[idx * 4 + g];
-    m.lpo = ga.logp_old[idx * 4 + g];
-    m.ret = ga.returns[idx];
-    m.adv = ga.adv[idx];
-    return m;
-  };
+  auto gather = [&](int c) { return gather_chunk<false, false>(ga, c, n, g); };  // (buffer order)
   int c = blockIdx.x * WAVES + wave;
   // the first chunk's rows are in flight while the weights are staged
   Smp nxt = gather(c < nchunks ? c : 0);
 
-  {  // the weight image, every thread's loads issued before its first LDS write
-    constexpr int NV = WEND / 4, PER = (NV + 64 * WAVES - 1) / (64 * WAVES);
-    f4 wv[PER];
-#pragma unroll
-    for (int i = 0; i < PER; i++) {
-      const int e = tid + i * 64 * WAVES;
-      if (e < NV) wv[i] = ((const f4*)ga.Wz)[e];
-    }
-#pragma unroll
-    for (int i = 0; i < PER; i++) {
-      const int e = tid + i * 64 * WAVES;
-      if (e < NV) ((f4*)lds)[e] = wv[i];
-    }
-  }
+  stage_weights<64 * WAVES>(ga.Wz, lds, tid);
   float* cb = lds + WEND + wave * SX;
   __syncthreads();
 
@@ -115,17 +84,13 @@ DEV void ppo_stats_pass(const StatsArgs& sa) {
     if (c + nw < nchunks) nxt = gather(c + nw);
     const int pos = c * 16 + n;
     const bool valid = pos < ga.samples;
-    {
-      const int h = (n >> 1) << 1;
-      const f4 v = (h & 2) ? f4{cur.sv[2], cur.sv[3], cur.sv[0], cur.sv[1]} : cur.sv;
-      *(f4*)(cb + n * 16 + ((4 * g) ^ (h & 12))) = v;
-    }
-    st_wave_sync();
+    sx_put(cb, n, g, cur.sv);
+    wave_sync();
     // ---- layer 1, actor and critic ----
     float sB[3];
 #pragma unroll
-    for (int t = 0; t < 3; t++) sB[t] = cb[st_sx(n, 4 * t + g)];
-    st_wave_sync();  // the tile is read: the next chunk may rewrite it
+    for (int t = 0; t < 3; t++) sB[t] = cb[sx(n, 4 * t + g)];
+    wave_sync();  // the tile is read: the next chunk may rewrite it
     f4 z1[4], zc1[4], h1[4], hc1[4];
 #pragma unroll
     for (int Mt = 0; Mt < 4; Mt++) { z1[Mt] = z4; zc1[Mt] = z4; }
@@ -133,8 +98,8 @@ DEV void ppo_stats_pass(const StatsArgs& sa) {
     for (int t = 0; t < 3; t++)
 #pragma unroll
       for (int Mt = 0; Mt < 4; Mt++) {
-        z1[Mt] = st_mfma(wa1[Mt][t], sB[t], z1[Mt]);
-        zc1[Mt] = st_mfma(wc1[Mt][t], sB[t], zc1[Mt]);
+        z1[Mt] = mfma(wa1[Mt][t], sB[t], z1[Mt]);
+        zc1[Mt] = mfma(wc1[Mt][t], sB[t], zc1[Mt]);
       }
 #pragma unroll
     for (int Mt = 0; Mt < 4; Mt++) {
@@ -144,8 +109,8 @@ DEV void ppo_stats_pass(const StatsArgs& sa) {
       for (int r = 0; r < 4; r++) {
         z1[Mt][r] = z1[Mt][r] + ba1[r];
         zc1[Mt][r] = zc1[Mt][r] + bc1[r];
-        h1[Mt][r] = st_lrelu(z1[Mt][r]);
-        hc1[Mt][r] = st_lrelu(zc1[Mt][r]);
+        h1[Mt][r] = mf_lrelu(z1[Mt][r]);
+        hc1[Mt][r] = mf_lrelu(zc1[Mt][r]);
       }
     }
     // ---- layer 2 (B operand = layer 1's D registers) ----
@@ -162,14 +127,14 @@ DEV void ppo_stats_pass(const StatsArgs& sa) {
 #pragma unroll
       for (int r = 0; r < 4; r++)
 #pragma unroll
-        for (int Mt = 0; Mt < 4; Mt++) z2[Mt] = st_mfma(w2[Mt][Mp][r], h1[Mp][r], z2[Mt]);
+        for (int Mt = 0; Mt < 4; Mt++) z2[Mt] = mfma(w2[Mt][Mp][r], h1[Mp][r], z2[Mt]);
 #pragma unroll
     for (int Mt = 0; Mt < 4; Mt++) {
       const f4 ba2 = *(const f4*)(lds + BA2 + 16 * Mt + 4 * g);
 #pragma unroll
       for (int r = 0; r < 4; r++) {
         z2[Mt][r] = z2[Mt][r] + ba2[r];
-        h2[Mt][r] = st_lrelu(z2[Mt][r]);
+        h2[Mt][r] = mf_lrelu(z2[Mt][r]);
       }
     }
     // ---- output rows: actor z3[0..3] on h2, critic V on hc1 ----
