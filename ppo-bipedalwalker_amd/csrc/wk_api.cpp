@@ -375,8 +375,7 @@ int wk_create(const wk_config* cfg, int device, int n_env, uint64_t seed, wk_ctx
     }
   }
   if (wk::launch_env_init(P, x->st, x->dxoff, nullptr, 0, x->stream) != hipSuccess ||
-      (x->general ? wk::launch_net_xavier(x->W, seed, x->net_dev, x->np, x->stream)
-                  : wk::launch_xavier(x->W, seed, x->stream)) != hipSuccess ||
+      wk::launch_xavier(x->W, seed, x->net.critic, x->net.actor, x->np, x->stream) != hipSuccess ||
       upload_image(x) != hipSuccess ||
       hipStreamSynchronize(x->stream) != hipSuccess) {
     x->err = "init kernels failed";

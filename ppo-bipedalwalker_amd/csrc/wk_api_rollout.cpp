@@ -78,12 +78,8 @@ int returns_impl(wk_ctx* c) {
   const float* rew = c->rn_on ? c->trs : c->tr;  // (reward normalisation: the scaled rewards)
   {
     ProfScope ps(c, PK_RET);
-    if (c->cfg.ReturnsMode == 1)
-      HIPCHK(c, wk::launch_returns_std(c->n, c->T_valid, c->cfg.UseGAE, c->cfg.Gamma, c->cfg.Lambda,
-                                       rew, c->tv, c->td, c->vlast, c->tret, c->tadv, c->stream));
-    else
-      HIPCHK(c, wk::launch_returns(c->n, c->T_valid, c->cfg.UseGAE, c->cfg.Gamma, c->cfg.Lambda,
-                                   rew, c->tv, c->td, c->tret, c->tadv, c->stream));
+    HIPCHK(c, wk::launch_returns(c->cfg.ReturnsMode, c->n, c->T_valid, c->cfg.UseGAE, c->cfg.Gamma,
+                                 c->cfg.Lambda, rew, c->tv, c->td, c->vlast, c->tret, c->tadv, c->stream));
   }
   if (c->cfg.NormalizeAdvantages)
     HIPCHK(c, wk::launch_normalize(c->tadv, c->n * c->T_valid, c->cfg.Epsilon, c->stream));

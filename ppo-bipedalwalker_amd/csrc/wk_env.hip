@@ -1,7 +1,7 @@
 // wk_env.hip -- the rollout's entry points: the dispatchers launch_env_step / launch_env_scene
 // over the kernel families (the other wk_env_*.hip units, declared in wk_kernels.h), the one- and
 // 16-lane kernels (k_env_step, wk_env_lane.h) with the counting replay, and the small kernels
-// around a rollout: init, observations, the standalone policy, returns.
+// around a rollout: init, observations, the standalone policy.
 #include "wk_env_lane.h"
 
 namespace wk {
@@ -54,37 +54,6 @@ __global__ void k_policy(EnvParams P, const float* __restrict__ W, float lp_cons
   }
 }
 
-// returns / advantages (PPOAgent.cs:175-189, 414-498), one lane per env, reverse scan
-// over the horizon; done[t] ends an episode at t.
-__global__ void k_returns(int n, int T, int use_gae, float gamma, float lambda,
-                          const float* __restrict__ r, const float* __restrict__ v,
-                          const uint8_t* __restrict__ done, float* ret, float* adv) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n) return;
-  if (!use_gae) {
-    float disc = 0.0f;
-    for (int t = T - 1; t >= 0; t--) {
-      size_t i = (size_t)t * n + e;
-      if (done[i]) disc = 0.0f;
-      disc = r[i] + (disc * gamma);
-      ret[i] = disc;
-      adv[i] = disc - v[i];
-    }
-  } else {
-    float nextGae = 0.0f, nextValue = 0.0f;
-    for (int t = T - 1; t >= 0; t--) {
-      size_t i = (size_t)t * n + e;
-      if (done[i]) nextValue = 0.0f;
-      float cur = v[i];
-      float delta = r[i] + (gamma * nextValue) - cur;
-      nextValue = cur;
-      float gae = delta + (gamma * lambda * nextGae);  // reference quirk: nextGae stays 0
-      adv[i] = gae;
-      ret[i] = gae + cur;
-    }
-  }
-}
-
 // host-side launch shims (C++ linkage, used by wk_api_env.cpp)
 hipError_t launch_env_scene(int mode, const EnvParams& P, const StepArgs& A, const SceneDev& S,
                             hipStream_t s) {
@@ -120,13 +89,6 @@ hipError_t launch_policy(const EnvParams& P, const float* W, float lp_const, int
                          float* mean, float* act, float* logp, float* v, hipStream_t s) {
   hipLaunchKernelGGL(k_policy, dim3((n + 63) / 64), dim3(64), 0, s, P, W, lp_const, n, obs,
                      env_ids, steps, mean, act, logp, v);
-  return hipGetLastError();
-}
-hipError_t launch_returns(int n, int T, int use_gae, float gamma, float lambda, const float* r,
-                          const float* v, const uint8_t* d, float* ret, float* adv,
-                          hipStream_t s) {
-  hipLaunchKernelGGL(k_returns, dim3((n + 255) / 256), dim3(256), 0, s, n, T, use_gae, gamma,
-                     lambda, r, v, d, ret, adv);
   return hipGetLastError();
 }
 }  // namespace wk

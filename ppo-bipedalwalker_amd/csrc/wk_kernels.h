@@ -1,5 +1,6 @@
-// wk_kernels.h -- kernel argument blocks and host launch shims shared by
-// the rollout units (wk_env*.hip), wk_ppo.hip and the host units (wk_api*.cpp).
+// wk_kernels.h -- kernel argument blocks and host launch shims: what every kernel unit (*.hip)
+// offers the host units (wk_api*.cpp) and the other kernel units.  One heading per unit, in the
+// Makefile's order; an argument block several units share comes before the first that takes it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -10,6 +11,7 @@
 
 namespace wk {
 
+// ---- the rollout units: wk_env_*.hip, wk_env.hip
 // per-substep pair bookkeeping; layout == wk_pair_trace (include/wk_api.h)
 struct PairTraceDev {
   uint8_t aabb_hit[9];
@@ -67,6 +69,12 @@ struct StepArgs {
   uint32_t pace_seq;
 };
 enum : int { PACE_SLOTS = 8 * 8 * 2 * 16 * 4 };  // XCC x SE x SH x CU x SIMD (HW_ID fields)
+// threads per block of the split (pair / quad) rollout kernels; wk_rollout_mapping reports the
+// launched grid from it
+#ifndef WK_SIDE_BLOCK
+#define WK_SIDE_BLOCK 256
+#endif
+constexpr int SIDE_BLOCK_THREADS = WK_SIDE_BLOCK;
 
 // scene props (wk_env_scene.h): Square / Triangle / Hexagon bodies after the floor, the same
 // shapes for every walker; per walker and prop k the state x[nv], y[nv], cx, cy, vx, vy, w,
@@ -82,6 +90,32 @@ struct SceneDev {
   float adx[SCENE_MAX_PROPS], ady[SCENE_MAX_PROPS];  // acceleration * deltaTime
 };
 
+hipError_t launch_env_step(int mode, const EnvParams& P, const StepArgs& A, hipStream_t s);
+hipError_t launch_env_scene(int mode, const EnvParams& P, const StepArgs& A, const SceneDev& S,
+                            hipStream_t s);
+// what the two dispatchers above (wk_env.hip) choose between: one kernel family per translation
+// unit, wk_env_pair.hip, wk_env_quad.hip, wk_env_side_rough.hip (k_env_side) and
+// wk_env_scene_{given,policy}[_rough].hip (k_env_scene), each built with its own switches and flags
+void launch_side_pair(int mode, const EnvParams& P, const StepArgs& A, hipStream_t s);
+void launch_side_quad(int mode, const EnvParams& P, const StepArgs& A, hipStream_t s);
+void launch_side_pair_rough(int mode, const EnvParams& P, const StepArgs& A, hipStream_t s);
+void launch_side_quad_rough(int mode, const EnvParams& P, const StepArgs& A, hipStream_t s);
+void launch_env_scene_given(int mode, const EnvParams& P, const StepArgs& A, const SceneDev& S,
+                            hipStream_t s);
+void launch_env_scene_policy(int mode, const EnvParams& P, const StepArgs& A, const SceneDev& S,
+                             hipStream_t s);
+void launch_env_scene_given_rough(int mode, const EnvParams& P, const StepArgs& A, const SceneDev& S,
+                                  hipStream_t s);
+void launch_env_scene_policy_rough(int mode, const EnvParams& P, const StepArgs& A, const SceneDev& S,
+                                   hipStream_t s);
+hipError_t launch_env_init(const EnvParams& P, float* st, const float* dx, const uint8_t* mask,
+                           int post, hipStream_t s);
+hipError_t launch_get_obs(const EnvParams& P, const float* st, float* obs, hipStream_t s);
+hipError_t launch_policy(const EnvParams& P, const float* W, float lp_const, int n,
+                         const float* obs, const int32_t* env_ids, const uint32_t* steps,
+                         float* mean, float* act, float* logp, float* v, hipStream_t s);
+
+// ---- the update path's argument blocks (wk_ppo*.hip, wk_tail.hip, wk_stats.hip, wk_net.hip)
 struct AdamArgs {
   float* W; float* m; float* v; const float* grad;
   float* Wz;  // operand-order image kept in step with W (or null)
@@ -117,40 +151,17 @@ struct GradArgs {
 // rows: the matrix-core kernel's block fold and slab stores are f4-wide)
 enum : int { SLAB = (NPARAM + 3 + 3) / 4 * 4 };
 static_assert(SLAB % 4 == 0 && SLAB >= NPARAM + 3, "slab layout");
-
-hipError_t launch_env_step(int mode, const EnvParams& P, const StepArgs& A, hipStream_t s);
-hipError_t launch_env_scene(int mode, const EnvParams& P, const StepArgs& A, const SceneDev& S,
-                            hipStream_t s);
-// what the two dispatchers above (wk_env.hip) choose between: one kernel family per translation
-// unit, wk_env_pair.hip, wk_env_quad.hip, wk_env_side_rough.hip (k_env_side) and
-// wk_env_scene_{given,policy}[_rough].hip (k_env_scene), each built with its own switches and flags
-void launch_side_pair(int mode, const EnvParams& P, const StepArgs& A, hipStream_t s);
-void launch_side_quad(int mode, const EnvParams& P, const StepArgs& A, hipStream_t s);
-void launch_side_pair_rough(int mode, const EnvParams& P, const StepArgs& A, hipStream_t s);
-void launch_side_quad_rough(int mode, const EnvParams& P, const StepArgs& A, hipStream_t s);
-void launch_env_scene_given(int mode, const EnvParams& P, const StepArgs& A, const SceneDev& S,
-                            hipStream_t s);
-void launch_env_scene_policy(int mode, const EnvParams& P, const StepArgs& A, const SceneDev& S,
-                             hipStream_t s);
-void launch_env_scene_given_rough(int mode, const EnvParams& P, const StepArgs& A, const SceneDev& S,
-                                  hipStream_t s);
-void launch_env_scene_policy_rough(int mode, const EnvParams& P, const StepArgs& A, const SceneDev& S,
-                                   hipStream_t s);
-hipError_t launch_env_init(const EnvParams& P, float* st, const float* dx, const uint8_t* mask,
-                           int post, hipStream_t s);
-hipError_t launch_get_obs(const EnvParams& P, const float* st, float* obs, hipStream_t s);
-hipError_t launch_policy(const EnvParams& P, const float* W, float lp_const, int n,
-                         const float* obs, const int32_t* env_ids, const uint32_t* steps,
-                         float* mean, float* act, float* logp, float* v, hipStream_t s);
-hipError_t launch_returns(int n, int T, int use_gae, float gamma, float lambda, const float* r,
-                          const float* v, const uint8_t* d, float* ret, float* adv, hipStream_t s);
 // the ordered reduction of a gradient launch's block slabs (wk_tail.h): groups of RG consecutive
 // slabs in order, then up to RG groups in order -- no gradient launch writes more slabs
 enum { RG = 16 };
 enum : int { GRAD_MAX_BLOCKS = RG * RG };
+
+// ---- wk_ppo.hip
 // the sequential lane-per-neuron kernel: one slab
 hipError_t launch_ppo_grad(GradArgs g, hipStream_t s);
 hipError_t configure_device_kernels();  // dynamic-LDS attributes, current device (wk_create)
+
+// ---- wk_ppo_mfma.hip
 hipError_t configure_mfma_kernels();
 // matrix-core gradient kernels: producer / consumer pairs (ws), tile-parallel teams of four
 // waves, two (tp) or one (tp1) per block, one wave per chunk (mf); GI_AUTO picks by size
@@ -161,11 +172,16 @@ hipError_t launch_ppo_grad_mfma(const GradArgs& g, int nblocks, int impl, hipStr
 hipError_t launch_swizzle(const float* W, float* Wz, hipStream_t s);
 int mfma_image_floats();
 int ppo_grad_mfma_blocks(int samples, int impl);
+
+// ---- wk_tail.hip: block slabs -> weight step
 // nblocks <= GRAD_MAX_BLOCKS slabs -> grad [SLAB]; adam: applied in the same launch, or null
 hipError_t launch_grad_reduce(const float* partial, int nblocks, float* grad, const AdamArgs* adam,
                               hipStream_t s);
+// the general networks' slabs (net_slab_floats(np) floats each); a.W set: Adam as well
+hipError_t launch_net_reduce(const float* partial, int nblocks, int np, float* grad, const AdamArgs& a,
+                             hipStream_t s);
 hipError_t launch_adam(const AdamArgs& a, hipStream_t s);
-// MaxGradNorm > 0 (k_clip_adam, wk_ppo.hip): per-network gradient-norm clipping and Adam over
+// MaxGradNorm > 0 (k_clip_adam): per-network gradient-norm clipping and Adam over
 // a.grad[0..np) of either kernel family, critic [0, n_critic) and actor [n_critic, np), and the
 // device record of the norms; layout == wk_grad_norms (include/wk_api.h)
 struct GradNormRec {
@@ -191,12 +207,6 @@ hipError_t launch_clip_adam(const AdamArgs& a, int np, int n_critic, float max_n
 // instead of applying it.  XCH_MAX_RANKS_PER_DEVICE: more ranks sharing one GPU stall (their
 // waiting exchange blocks hold the CUs a peer's gradient kernel needs), so wk_comm_init_ipc
 // refuses them.
-// threads per block of the split (pair / quad) rollout kernels; wk_rollout_mapping reports the
-// launched grid from it
-#ifndef WK_SIDE_BLOCK
-#define WK_SIDE_BLOCK 256
-#endif
-constexpr int SIDE_BLOCK_THREADS = WK_SIDE_BLOCK;
 enum : int { XCH_FLAGS = 128, XCH_MAX_RANKS = 8, XCH_MAX_RANKS_PER_DEVICE = 4 };
 constexpr double XCH_TIMEOUT_S_DEFAULT = 30.0;
 constexpr double XCH_TICKS_PER_S = 1.0e8;
@@ -223,54 +233,16 @@ enum : int { XCH_POINTS = 4 };
 int xch_blocks();
 size_t xch_region_bytes();
 hipError_t launch_reduce_xch_adam(const XchArgs& x, hipStream_t s);
+
+// ---- wk_returns.hip: returns and advantages over the [T][n] rows.  mode: ReturnsMode -- 0 the
+// reference's scan (k_returns), 1 chained GAE(lambda) and the scan bootstrapped from vlast[n]
+// (k_returns_std), the only mode that reads vlast
+hipError_t launch_returns(int mode, int n, int T, int use_gae, float gamma, float lambda, const float* r,
+                          const float* v, const uint8_t* d, const float* vlast, float* ret, float* adv,
+                          hipStream_t s);
 hipError_t launch_normalize(float* x, int n, float eps, hipStream_t s);
-// ReturnsMode = 1 (k_returns_std): chained GAE(lambda), the scan bootstrapped from vlast[n]
-hipError_t launch_returns_std(int n, int T, int use_gae, float gamma, float lambda, const float* r,
-                              const float* v, const uint8_t* d, const float* vlast, float* ret,
-                              float* adv, hipStream_t s);
-hipError_t launch_xavier(float* W, uint64_t seed, hipStream_t s);
 
-// Reward normalisation (wk_reward_norm_*; wk_rnorm.hip): rewards scaled by the running standard
-// deviation of the walkers' discounted returns, into a second reward buffer that only the returns
-// kernels read.  RnormRec is the device record; layout == wk_reward_norm (include/wk_api.h), the
-// configuration fields (clip, epsilon, enabled, frozen) filled by the host when it is read.
-struct RnormRec {
-  long long count;
-  double mean, m2, var;
-  float scale, clip, epsilon;
-  int32_t enabled, frozen, pad;
-  long long rows, clipped, nonfinite;
-};
-static_assert(sizeof(RnormRec) == 80, "RnormRec is wk_reward_norm");
-// the scan's tile: RNORM_TILE walkers, one lane each, fold to one partial of RNORM_FIELDS 64-bit
-// words (samples, non-finite samples as integers; sum x, sum x^2 as doubles).  The association is
-// a function of n alone: a tree over the tile's lanes, then the tiles in tile order.
-enum : int { RNORM_TILE = 256, RNORM_FIELDS = 4 };
-int rnorm_tiles(int n);
-// the full pass: scan (acc carried, partial[rnorm_tiles(n)][RNORM_FIELDS]), finish (the merge into
-// rec and the new scale), apply (out = clamp(r * rec->scale)).  learn = false: finish only clears
-// the last pass's counters and the scan does not run -- the apply step with the scale as it is.
-hipError_t launch_rnorm_pass(int n, int T, float gamma, float clip, float epsilon, bool learn,
-                             const float* r, const uint8_t* done, float* acc,
-                             unsigned long long* partial, RnormRec* rec, float* out, hipStream_t s);
-hipError_t launch_rnorm_reset(int n, const uint8_t* mask, float* acc, hipStream_t s);
-
-// the general networks' kernels (wk_net.hip; NetworkKernels = 1).  nets: device copy of
-// {critic, actor}; act_rows: net_act_rows of the two
-enum : int { NET_MAX_BLOCKS = 1024 };  // gradient blocks (one slab each) per minibatch
-hipError_t configure_net_kernels();
-int net_act_rows(const NetDesc& critic, const NetDesc& actor);
-int net_slab_floats(int np);
-int net_grad_blocks(int samples);
-hipError_t launch_net_policy(const EnvParams& P, const NetDesc* nets, int act_rows, const float* W,
-                             float lp_const, int n, const float* obs, const int32_t* env_ids,
-                             const uint32_t* steps, float* mean, float* act, float* logp, float* v,
-                             hipStream_t s);
-hipError_t launch_net_grad(const GradArgs& g, const NetDesc* nets, int act_rows, int np, hipStream_t s);
-hipError_t launch_net_reduce(const float* partial, int nblocks, int np, float* grad, const AdamArgs& a,
-                             hipStream_t s);
-hipError_t launch_net_xavier(float* W, uint64_t seed, const NetDesc* nets, int np, hipStream_t s);
-
+// ---- wk_stats.hip
 // Policy statistics over the trajectory (wk_policy_stats; k_ppo_stats in wk_stats.hip for the
 // built-in networks, k_net_stats in wk_net.hip for the general ones, wk_stats.h the arithmetic
 // they share).  StatsRec is the record every stage carries -- counts as integers, sums in double,
@@ -304,15 +276,86 @@ struct StatsArgs {
   float* values_new;        // [rows] or null
   unsigned long long* partial;  // [blocks][STATS_FIELDS], log_std: [blocks][STATS_FIELDS_LS]
 };
-// log_std: the <true> instantiation and its record width, in all three launches
+// log_std: the <true> instantiation and its record width, in all three launches (with wk_net.hip's)
 int ppo_stats_blocks(int rows);
 hipError_t launch_ppo_stats(const StatsArgs& a, int nblocks, bool log_std, hipStream_t s);
-int net_stats_blocks(int rows);
-hipError_t launch_net_stats(const StatsArgs& a, const NetDesc* nets, int act_rows, bool log_std,
-                            hipStream_t s);
 hipError_t launch_stats_finish(const unsigned long long* partial, int nblocks, bool log_std, void* out,
                                hipStream_t s);
 
+// ---- wk_rnorm.hip
+// Reward normalisation (wk_reward_norm_*; wk_rnorm.hip): rewards scaled by the running standard
+// deviation of the walkers' discounted returns, into a second reward buffer that only the returns
+// kernels read.  RnormRec is the device record; layout == wk_reward_norm (include/wk_api.h), the
+// configuration fields (clip, epsilon, enabled, frozen) filled by the host when it is read.
+struct RnormRec {
+  long long count;
+  double mean, m2, var;
+  float scale, clip, epsilon;
+  int32_t enabled, frozen, pad;
+  long long rows, clipped, nonfinite;
+};
+static_assert(sizeof(RnormRec) == 80, "RnormRec is wk_reward_norm");
+// the scan's tile: RNORM_TILE walkers, one lane each, fold to one partial of RNORM_FIELDS 64-bit
+// words (samples, non-finite samples as integers; sum x, sum x^2 as doubles).  The association is
+// a function of n alone: a tree over the tile's lanes, then the tiles in tile order.
+enum : int { RNORM_TILE = 256, RNORM_FIELDS = 4 };
+int rnorm_tiles(int n);
+// the full pass: scan (acc carried, partial[rnorm_tiles(n)][RNORM_FIELDS]), finish (the merge into
+// rec and the new scale), apply (out = clamp(r * rec->scale)).  learn = false: finish only clears
+// the last pass's counters and the scan does not run -- the apply step with the scale as it is.
+hipError_t launch_rnorm_pass(int n, int T, float gamma, float clip, float epsilon, bool learn,
+                             const float* r, const uint8_t* done, float* acc,
+                             unsigned long long* partial, RnormRec* rec, float* out, hipStream_t s);
+hipError_t launch_rnorm_reset(int n, const uint8_t* mask, float* acc, hipStream_t s);
+
+// ---- wk_net.hip
+// the general networks' kernels (wk_net.hip; NetworkKernels = 1).  nets: device copy of
+// {critic, actor}; act_rows: net_act_rows of the two
+enum : int { NET_MAX_BLOCKS = 1024 };  // gradient blocks (one slab each) per minibatch
+hipError_t configure_net_kernels();
+int net_act_rows(const NetDesc& critic, const NetDesc& actor);
+int net_slab_floats(int np);
+int net_grad_blocks(int samples);
+hipError_t launch_net_policy(const EnvParams& P, const NetDesc* nets, int act_rows, const float* W,
+                             float lp_const, int n, const float* obs, const int32_t* env_ids,
+                             const uint32_t* steps, float* mean, float* act, float* logp, float* v,
+                             hipStream_t s);
+hipError_t launch_net_grad(const GradArgs& g, const NetDesc* nets, int act_rows, int np, hipStream_t s);
+int net_stats_blocks(int rows);
+hipError_t launch_net_stats(const StatsArgs& a, const NetDesc* nets, int act_rows, bool log_std,
+                            hipStream_t s);
+// Xavier-normal init of W[0..np), both kernel families (a built-in context: the default strings')
+hipError_t launch_xavier(float* W, uint64_t seed, const NetDesc& critic, const NetDesc& actor, int np,
+                         hipStream_t s);
+
+// ---- wk_episodes.hip
+// data collection: per-episode totals of a recorded rollout appended to the device log;
+// layout == wk_episode_rec (include/wk_api.h)
+struct EpisodeRecDev {
+  float total_reward;
+  int32_t env;
+  int32_t length;
+  uint32_t step;
+};
+struct EpisodeArgs {
+  int n, T, env_offset;
+  uint32_t step0;             // rollout env-steps taken before this one
+  const float* rewards;      // [T][n]
+  const uint8_t* dones;      // [T][n]
+  double* acc;               // [n] running episode reward (carried across rollouts)
+  int32_t* len;              // [n] running episode length
+  float2* scratch;           // [T][n] (total, length bits), written where done
+  uint32_t* row_cnt;         // [episode_count_cells(n, T)], zero on entry and exit
+  uint64_t* log_count;       // records appended so far (may exceed cap: dropped)
+  uint64_t cap;
+  EpisodeRecDev* log;
+};
+hipError_t launch_episode_log(const EpisodeArgs& a, hipStream_t s);
+int episode_count_cells(int n, int T);
+hipError_t launch_episode_reset(int n, const uint8_t* mask, double* acc, int32_t* len,
+                                hipStream_t s);
+
+// ---- wk_eval.hip
 // Policy evaluation (wk_evaluate; wk_eval.hip).  The accounting kernel k_eval_step runs after
 // every env-step of the evaluation's private walker records, on SoA per-walker state; k_eval_fold
 // and k_eval_finish fold the [episodes][n] records with the discipline of wk_stats.h (integers and
@@ -363,34 +406,10 @@ hipError_t launch_eval_fold(const EvalRecDev* recs, const uint32_t* fault, int n
                             unsigned long long* partial /* [blocks][EVAL_FIELDS] */,
                             unsigned long long* out /* [EVAL_FIELDS] */, hipStream_t s);
 
-// data collection: per-episode totals of a recorded rollout appended to the device log;
-// layout == wk_episode_rec (include/wk_api.h)
-struct EpisodeRecDev {
-  float total_reward;
-  int32_t env;
-  int32_t length;
-  uint32_t step;
-};
-struct EpisodeArgs {
-  int n, T, env_offset;
-  uint32_t step0;             // rollout env-steps taken before this one
-  const float* rewards;      // [T][n]
-  const uint8_t* dones;      // [T][n]
-  double* acc;               // [n] running episode reward (carried across rollouts)
-  int32_t* len;              // [n] running episode length
-  float2* scratch;           // [T][n] (total, length bits), written where done
-  uint32_t* row_cnt;         // [episode_count_cells(n, T)], zero on entry and exit
-  uint64_t* log_count;       // records appended so far (may exceed cap: dropped)
-  uint64_t cap;
-  EpisodeRecDev* log;
-};
-hipError_t launch_episode_log(const EpisodeArgs& a, hipStream_t s);
+// ---- wk_order.hip
 // lane order for k_env_side: episode-0 walkers first, then the post-reset ones (wk_order.hip)
 int order_cells(int n);  // counters: one per tile of 1,024 slots + the swap count
 hipError_t launch_walker_order(const float* st, int n, uint32_t* cnt, int32_t* order,
                                int32_t* scratch /* [2 n] */, hipStream_t s);
-int episode_count_cells(int n, int T);
-hipError_t launch_episode_reset(int n, const uint8_t* mask, double* acc, int32_t* len,
-                                hipStream_t s);
 
 }  // namespace wk

@@ -26,7 +26,6 @@
 #include "wk_net.h"
 #include "wk_sample.h"
 #include "wk_stats.h"
-#include "wk_tail.h"
 
 namespace wk {
 
@@ -429,40 +428,17 @@ __global__ __launch_bounds__(64) void k_net_grad(NetGradArgs A) {
   }
 }
 
-// The slabs in block order (groups of RG consecutive slabs, then the groups: wk_tail.h's
-// association) and, with a.W set, DenseLayer.Adam (DenseLayer.cs:125-159) on the np parameters
-__global__ void k_net_reduce(const float* __restrict__ partial, int nblocks, int slabn, int np,
-                             float* grad, AdamArgs a) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= slabn) return;
-  const bool adam = a.W != nullptr && p < np;
-  float m0 = 0.0f, v0 = 0.0f, w0 = 0.0f;
-  if (adam) { m0 = a.m[p]; v0 = a.v[p]; w0 = a.W[p]; }
-  float sum = 0.0f;
-#pragma unroll 1
-  for (int b0 = 0; b0 < nblocks; b0 += RG) {
-    float v[RG];
-#pragma unroll
-    for (int j = 0; j < RG; j++) v[j] = (b0 + j < nblocks) ? partial[(size_t)(b0 + j) * slabn + p] : 0.0f;
-    float acc = 0.0f;
-#pragma unroll
-    for (int j = 0; j < RG; j++)
-      if (b0 + j < nblocks) acc = acc + v[j];
-    sum = sum + acc;
-  }
-  grad[p] = sum;
-  if (adam) adam_apply(a, p, sum, m0, v0, w0);
-}
-
-// Matrix.FromXavier (Matrix.cs:59-80) per dense layer, k_xavier's arithmetic: element k of the
-// l-th dense layer (critic first) draws philox(seed, k, l, 0, ST_XAVIER); biases are zero
-__global__ void k_net_xavier(float* W, uint64_t seed, const NetDesc* __restrict__ nets, int np) {
+// Xavier-normal init (Matrix.FromXavier, Matrix.cs:59-80) on the device, for both kernel families
+// (a built-in context passes the default strings' descriptions): element k of the l-th dense
+// layer (critic first) draws philox(seed, k, l, 0, ST_XAVIER); biases are zero.  The two
+// descriptions travel by value as kernel arguments, so the launch reads no device copy of them.
+__global__ void k_xavier(float* W, uint64_t seed, NetDesc critic, NetDesc actor, int np) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= np) return;
   float v = 0.0f;
   int gl = 0;
   for (int q = 0; q < 2; q++) {
-    const NetDesc* d = nets + q;
+    const NetDesc* d = q == 0 ? &critic : &actor;
     for (int l = 0; l < d->n_layers; l++) {
       const NetLayer L = d->layer[l];
       if (L.kind != NL_DENSE) continue;
@@ -559,16 +535,9 @@ hipError_t launch_net_stats(const StatsArgs& a, const NetDesc* nets, int act_row
   return hipGetLastError();
 }
 
-hipError_t launch_net_reduce(const float* partial, int nblocks, int np, float* grad, const AdamArgs& a,
-                             hipStream_t s) {
-  const int slabn = net_slab_floats(np);
-  hipLaunchKernelGGL(k_net_reduce, dim3((slabn + 255) / 256), dim3(256), 0, s, partial, nblocks, slabn,
-                     np, grad, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_net_xavier(float* W, uint64_t seed, const NetDesc* nets, int np, hipStream_t s) {
-  hipLaunchKernelGGL(k_net_xavier, dim3((np + 255) / 256), dim3(256), 0, s, W, seed, nets, np);
+hipError_t launch_xavier(float* W, uint64_t seed, const NetDesc& critic, const NetDesc& actor, int np,
+                         hipStream_t s) {
+  hipLaunchKernelGGL(k_xavier, dim3((np + 255) / 256), dim3(256), 0, s, W, seed, critic, actor, np);
   return hipGetLastError();
 }
 

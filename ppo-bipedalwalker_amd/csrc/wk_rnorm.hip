@@ -2,13 +2,13 @@
 // buffer scaled by the running standard deviation of the walkers' discounted returns, written to a
 // second [T][n] buffer that only the returns kernels read.  Three launches:
 //
-//   k_rnorm_scan    one lane per walker (k_returns' mapping: row t of [t][e] is read coalesced),
-//                   forward over t: x = r + (a * gamma) in fp32, uncontracted, as k_returns forms
-//                   r + disc * gamma; a finite x adds 1, (double)x and (double)x * (double)x (the
-//                   double square of a float is exact) to the lane's count and sums and becomes the
-//                   carry a, any other x is counted and zeroes the carry; a terminal row zeroes the
-//                   carry; the carry goes back to acc[e].  A tile of RNORM_TILE lanes folds through
-//                   LDS in a fixed tree to one partial.
+//   k_rnorm_scan    one lane per walker (returns_scan's mapping, wk_returns.hip: row t of [t][e] is
+//                   read coalesced), forward over t: x = r + (a * gamma) in fp32, uncontracted, as
+//                   returns_scan forms r + disc * gamma; a finite x adds 1, (double)x and
+//                   (double)x * (double)x (the double square of a float is exact) to the lane's
+//                   count and sums and becomes the carry a, any other x is counted and zeroes the
+//                   carry; a terminal row zeroes the carry; the carry goes back to acc[e].  A tile
+//                   of RNORM_TILE lanes folds through LDS in a fixed tree to one partial.
 //   k_rnorm_finish  one block: the tiles' partials in a fixed order, the batch's moments, Chan's
 //                   merge into the running (count, mean, m2) in double, the new scale.
 //   k_rnorm_apply   the streaming pass y = r * scale (one fp32 product), clamped to +-clip by

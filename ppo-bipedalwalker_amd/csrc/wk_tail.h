@@ -1,4 +1,4 @@
-// wk_tail.h -- the minibatch tail of the reduction kernels (wk_ppo.hip): the ordered two-level
+// wk_tail.h -- the minibatch tail of the reduction kernels (wk_tail.hip): the ordered two-level
 // sum of the gradient kernels' block slabs and DenseLayer.Adam (DenseLayer.cs:125-159).  (Round 5
 // also fused it into the gradient kernels' last-arriving blocks: bit-identical, +4.5 us per
 // minibatch, profiles/r05_tail_ab.txt -- removed in round 6; the launch boundary is cheaper.)

@@ -1,4 +1,4 @@
-"""What MaxGradNorm costs (k_clip_adam, csrc/wk_ppo.hip), one GPU, at bench.py's shape (65,536
+"""What MaxGradNorm costs (k_clip_adam, csrc/wk_tail.hip), one GPU, at bench.py's shape (65,536
 walkers, T_h 64, M 65,536, 5 epochs: 320 Adam steps per update).
 
   1. wk_ppo_update with MaxGradNorm in {0, inf, 0.5} on the built-in kernels and on the general

@@ -1,4 +1,4 @@
-"""Restatement of MaxGradNorm (include/wk_api.h, k_clip_adam in csrc/wk_ppo.hip) -- test
+"""Restatement of MaxGradNorm (include/wk_api.h, k_clip_adam in csrc/wk_tail.hip) -- test
 infrastructure only (numpy).  Per network (critic = parameters [0, n_critic), actor the rest):
 
     norm  = sqrt(sum (double)g * (double)g)       g the fp32 summed gradient

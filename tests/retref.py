@@ -1,10 +1,10 @@
 """Restatement of the returns / advantages scans -- test infrastructure only (numpy).
 
-  * returns32(mode, ...): float32, operation for operation as the kernels: mode 0 restates
-    k_returns (csrc/wk_env.hip: the reference's PPOAgent.cs:414-498, whose GAE chain is never
-    carried and whose scans start from 0), mode 1 restates k_returns_std (csrc/wk_ppo.hip: chained
-    GAE(lambda), the scan started from vlast).  The library is built without contraction, so every
-    product and sum below rounds once, as on the GPU.
+  * returns32(mode, ...): float32, operation for operation as the kernels' one scan
+    (returns_scan<STD>, csrc/wk_returns.hip): mode 0 restates k_returns (the reference's
+    PPOAgent.cs:414-498, whose GAE chain is never carried and whose scans start from 0), mode 1
+    restates k_returns_std (chained GAE(lambda), the scan started from vlast).  The library is built
+    without contraction, so every product and sum below rounds once, as on the GPU.
   * returns64(mode, ...): the same scans in float64.
   * normalize32: k_normalize (PPOAgent.cs:461-472; mean and variance accumulate in double).
   * normalize_case: the advantages the k_normalize tests share between the GPU comparison and the

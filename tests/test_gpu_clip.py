@@ -1,5 +1,5 @@
 """GPU: MaxGradNorm (per-network gradient-norm clipping in the Adam step, k_clip_adam in
-csrc/wk_ppo.hip), its record (wk_grad_norms_get) and wk_set_learning_rate, on the built-in and the
+csrc/wk_tail.hip), its record (wk_grad_norms_get) and wk_set_learning_rate, on the built-in and the
 general kernels, against the restatement tests/clipref.py.
 
 Inputs: net_cases.draw(name, B, 3000 + B) with the returns multiplied by RET_SCALE = 100, chosen on

@@ -37,7 +37,7 @@ def _free_port():
 
 
 def _adam_t1(w, g, alpha=np.float32(0.001), beta1=0.9, beta2=0.999, eps=np.float32(1e-8)):
-    """DenseLayer.Adam at t = 1 from zero moments, op for op as adam_param (wk_ppo.hip)"""
+    """DenseLayer.Adam at t = 1 from zero moments, op for op as adam_apply (wk_tail.h)"""
     f = np.float32
     c1, c2 = f(1.0) - f(beta1), f(1.0) - f(beta2)
     bc1 = f(1.0 - np.float64(f(beta1)) ** 1)

@@ -19,6 +19,8 @@ float64 take different branches of the derivative: such a sample is a property o
 Widths at the tile edges, the block / reduction-group edges, more skip patterns, the surrogate's six
 cells, Adam's moments and rollouts across episode ends: tests/test_gpu_net_edges.py.
 """
+import os
+
 import numpy as np
 import pytest
 
@@ -58,10 +60,17 @@ def _forward(name, w, S):
 
 # ---- 1. init ----
 def test_init_default_equals_builtin(wk):
+    """Both families launch the one k_xavier with the default strings' descriptions, so comparing
+    the two contexts cannot fail on its own: both are also held to the recorded bytes of the
+    built-in table kernel k_xavier replaced (tests/golden/xavier_builtin_seed20250908.npy: that
+    kernel's get_weights() of a fresh 4-walker context with this seed, on an MI355X)."""
     a = wk.Engine(4, seed=SEED + 3)
     b = _engine(wk, "default")
     b2 = wk.Engine(4, seed=SEED + 3, NetworkKernels=1)
     assert b.nparam == wk.NPARAM and b.grad_kernel() == "k_net_grad" and a.grad_kernel(64) != "k_net_grad"
+    recorded = np.load(os.path.join(os.path.dirname(__file__), "golden", "xavier_builtin_seed20250908.npy"))
+    assert recorded.dtype == F and recorded.shape == (wk.NPARAM,)
+    np.testing.assert_array_equal(a.get_weights().view(np.uint32), recorded.view(np.uint32))
     np.testing.assert_array_equal(a.get_weights(), b2.get_weights())
     assert not np.array_equal(a.get_weights(), b.get_weights())  # another seed
 

@@ -1,8 +1,10 @@
-"""GPU: ReturnsMode = 1 -- k_returns_std (csrc/wk_ppo.hip), the bootstrap values and their calls.
+"""GPU: ReturnsMode = 1 -- k_returns_std (csrc/wk_returns.hip), the bootstrap values and their
+calls; and ReturnsMode = 0's k_returns, the same scan's other instantiation, bit for bit.
 
-  * the kernel against the float32 restatement (tests/retref.py), bit for bit, on caller data:
+  * both kernels against the float32 restatement (tests/retref.py), bit for bit, on caller data:
     n in {1, 63, 64, 65, 257} (257 crosses the 256-lane block), T in {1, 2, 64} at Horizon 64,
-    Monte-Carlo and GAE, five done patterns;
+    Monte-Carlo and GAE, five done patterns; the bootstrap value is in mode 1's last row and not
+    in mode 0's;
   * non-finite bootstrap values: nothing passes an episode end, and a NaN stays in its column;
   * NormalizeAdvantages on top (k_normalize, unchanged) at the bar tests/test_gpu_parity.py
     applies to normalised advantages: rtol 1e-5, atol 1e-6; and k_normalize alone from one element
@@ -52,14 +54,17 @@ def _inputs(T, n, g):
     return r, v, vlast
 
 
-def _run(eng, r, v, d, vlast):
-    """set_trajectory + set_bootstrap_values + compute_returns + get_trajectory"""
+def _run(eng, r, v, d, vlast, mode=1):
+    """set_trajectory + set_bootstrap_values (ReturnsMode 1 only: a mode-0 context has none) +
+    compute_returns + get_trajectory"""
     T, n = r.shape
     eng.set_trajectory(np.zeros((T, n, 12), F), np.zeros((T, n, 4), F), np.zeros((T, n, 4), F), r, d, v)
-    eng.set_bootstrap_values(vlast)
+    if mode == 1:
+        eng.set_bootstrap_values(vlast)
     eng.compute_returns()
     tr = eng.get_trajectory(T)
-    np.testing.assert_array_equal(_bits(eng.get_bootstrap_values()), _bits(vlast))
+    if mode == 1:
+        np.testing.assert_array_equal(_bits(eng.get_bootstrap_values()), _bits(vlast))
     return tr["returns"], tr["advantages"]
 
 
@@ -71,21 +76,29 @@ def _expect_wk_error(wk, code, fn, *a, word=None):
         assert word in str(ex.value), str(ex.value)
 
 
-@pytest.mark.parametrize("use_gae", [0, 1])
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 257])
-def test_kernel_equals_restatement_bit_for_bit(wk, n, use_gae):
-    eng = wk.Engine(n, seed=SEED, Horizon=64, ReturnsMode=1, UseGAE=use_gae)
+# both ReturnsMode values: the two kernels are one scan's text (returns_scan<STD>).  The mode-1 cases
+# keep the ids they had before the test took a mode ("n-use_gae"); the mode-0 cases add "-mode0".
+_BITWISE = [(n, use_gae, mode) for mode in (1, 0) for n in (1, 63, 64, 65, 257) for use_gae in (0, 1)]
+
+
+@pytest.mark.parametrize("n,use_gae,mode", _BITWISE,
+                         ids=[f"{n}-{u}" + ("" if m == 1 else "-mode0") for n, u, m in _BITWISE])
+def test_kernel_equals_restatement_bit_for_bit(wk, n, use_gae, mode):
+    eng = wk.Engine(n, seed=SEED, Horizon=64, ReturnsMode=mode, UseGAE=use_gae)
     g = np.random.default_rng(1000 * n + use_gae)
     for T in (1, 2, 64):
         for pattern in PATTERNS:
             r, v, vlast = _inputs(T, n, g)
             d = _dones(pattern, T, n, g)
-            ret, adv = _run(eng, r, v, d, vlast)
-            xret, xadv = retref.returns32(1, use_gae, GAMMA, LAMBDA, r, v, d, vlast)
+            ret, adv = _run(eng, r, v, d, vlast, mode)
+            xret, xadv = retref.returns32(mode, use_gae, GAMMA, LAMBDA, r, v, d, vlast)
             np.testing.assert_array_equal(_bits(ret), _bits(xret), err_msg=f"ret T={T} {pattern}")
             np.testing.assert_array_equal(_bits(adv), _bits(xadv), err_msg=f"adv T={T} {pattern}")
-            if pattern == "none":  # the bootstrap value is in the last row (a step of 0.9)
+            if pattern == "none" and mode == 1:  # the bootstrap value is in the last row (a step of 0.9)
                 other = retref.returns32(1, use_gae, GAMMA, LAMBDA, r, v, d, vlast + F(1))[0]
+                assert (other[T - 1] != ret[T - 1]).all()
+            elif pattern == "none":  # mode 0 starts from 0: no bootstrap value is in the last row
+                other = retref.returns32(1, use_gae, GAMMA, LAMBDA, r, v, d, vlast)[0]
                 assert (other[T - 1] != ret[T - 1]).all()
     eng.close()
 
