@@ -22,6 +22,9 @@
  *   wk_set_materials           Walker._material : IMaterial (Walker.cs:17,30; Materials/<Name>.cs)
  *   wk_get_body_view           RigidBody.GetVectors/GetCentroid/... for Renderer and
  *                              ConsoleRenderer (Bodies/RigidBody.cs:191-261)
+ *   wk_render, _device, _states Environment.RenderObjects (Environment.cs:189-208) as RGBA frames
+ *                              of any list of walkers: RenderRigidObject, RenderJoints
+ *                              (Rendering/Renderer.cs:90-108), GetJointColors (Walker.cs:86-99)
  *   wk_policy_sample           PPOAgent.SampleActions (PPOAgent.cs:381-398)
  *   wk_value                   PPOAgent.GetValueEstimate (PPOAgent.cs:350-364)
  *   wk_rollout                 Environment.Update x horizon with Trajectory recording
@@ -747,6 +750,92 @@ int wk_evaluate(wk_ctx* ctx, const wk_eval_args* args /* NULL = defaults */, wk_
  * context's stream (mean duration per launch, as wk_time_gradient).  Touches nothing but that
  * block. */
 int wk_evaluate_time(wk_ctx* ctx, int reps, double* step_ms, double* fold_ms);
+
+/* Frames (the engine's counterpart of Environment.RenderObjects, Environment.cs:189-208: every
+ * rigid body as a closed polyline, Renderer.RenderRigidObject Rendering/Renderer.cs:90-99; the four
+ * joints as squares coloured by their torque, Walker.GetJointColors Walker/Walker.cs:86-99; the
+ * best-distance marker, Environment.cs:197-199).  One launch draws n_views walkers of the context
+ * into RGBA frames on the device, from the records, materials, props and terrain the context
+ * already holds -- a contact sheet, a film of saved states, image observations.  Windowing and
+ * input stay outside the engine.
+ *
+ * Layout.  [view][row j][column i][R, G, B, A] bytes, A = 255 everywhere, row 0 at the top; world y
+ * grows downward (the floor is at y = 900), as on the reference's screen.  Background (0, 0, 0).
+ * Every byte of every view is written, so the image needs no clear.
+ *
+ * Transform (fp32, nothing fused or re-associated): u = (x - ox_view) * scale, v = (y - oy) *
+ * scale, with ox_view = ox, or with follow ox_view = (posx - 0.5f * ((float)width / scale)) + ox,
+ * posx the record's WK_ST_POS.
+ *
+ * Primitive.  A segment is (a, b, colour, thickness tau in pixels), a and b in pixel coordinates.
+ * With d = b - a, L2 = d.x d.x + d.y d.y, c = (i + 0.5f, j + 0.5f), e = c - a, t = e.x d.x + e.y d.y
+ * and cr = e.x d.y - e.y d.x, pixel (i, j) is covered exactly when L2 > 0, t >= 0, t < L2 and cr cr <
+ * (0.25f tau tau) L2: a rectangle of length |d| and width tau around the segment, half-open along
+ * it -- the shape of the reference's scaled 1 x 1 sprite (Renderer.cs:119-124) without its
+ * sub-pixel sampling rules.  No square root, no divide.  A NaN fails every comparison, so a
+ * non-finite vertex draws nothing and never faults.
+ *
+ * Painter's order: the covering segment with the highest index gives the colour.  In order:
+ *   1. with `joints`, 16 edges: per joint k of Walker._joints (Walker.cs:182-187; 0 BODY v1 - LLU v4,
+ *      1 BODY v1 - RLU v4, 2 LLU v2 - LLL v3, 3 RLU v2 - RLL v3) the square of side 3 world units
+ *      about (A + B) / 2f with Renderer.DrawSquare's corners (Renderer.cs:127-135), thickness 2
+ *      line_px, colour R = (int)(value 255f + 0.5f), G = 0, B = (int)((1f - value) 255f + 0.5f) with
+ *      value = (1f + clamp(torque_k, -1, 1)) / 2f, a NaN torque counting as 0;
+ *   2. with a marker_x that is not NaN, the Lime segment (marker_x, 500) - (marker_x, 900), thickness
+ *      2 line_px;
+ *   3. the floor, White: 4 edges, or with RoughFloor the 10 segments x 4 edges in segment order
+ *      (wk_get_body_view's vertices; the terrain is regenerated on the device);
+ *   4. LLL, LLU, BODY, RLL, RLU (6, 6, 5, 6, 6 edges, vertex k to vertex (k + 1) mod n) in the
+ *      walker's material colour: Gray (128,128,128) for Carpet, Rubber, Paper and SuperRubber, Cyan
+ *      (0,255,255) Ice, White Metal, SandyBrown (244,164,96) Wood, SlateGray (112,128,144) Titanium
+ *      (Materials/<Name>.cs, XNA's named colours);
+ *   5. the props in scene order, a static one White, a dynamic one in its material's colour.
+ * Outlines have thickness line_px.  At most 16 + 1 + 40 + 29 + 32 = 118 segments per view.  The
+ * order is fixed, where the reference's list order flips after a reset (wk_body_order).
+ *
+ * wk_render draws the context's current records of the listed walkers (repeats allowed, every view
+ * independent), stream-ordered on the context's stream -- after an asynchronous wk_rollout it shows
+ * the state after that rollout -- then copies the frames to the host and synchronises.
+ * wk_render_device is the same without the copy and without a synchronise: d_rgba is device memory,
+ * 4-byte aligned (one packed store per pixel).  The walker ids are a HOST array in every variant, so
+ * every index the kernel uses has been checked; they are copied to a buffer the context keeps.
+ * That copy (and wk_render_states' copy of the records) is a stream-ordered host-to-device copy
+ * from the caller's pageable array: the array may be reused as soon as the call returns, and
+ * the runtime is free to stage it and to wait for earlier work on the stream before returning, so
+ * "no synchronise" means the call never waits for its own kernel, not that it can never block.
+ * The burst scripts/render_episode.py --bench times includes this copy in every call.
+ * wk_render_states draws host records (wk_get_state's layout) as if walker envs[i] had record
+ * states[i]: material, terrain and props are walker envs[i]'s as they are now.  It only draws, so
+ * wk_set_state's pole rule is not checked.
+ * No call changes anything a later call can observe: walker records, Philox counters, trajectory
+ * buffer (validity and bootstrap values included), logs, weights, Adam, the snapshot slot, the
+ * reward normalisation, the wk_profile totals.  Every context: both kernel families, every
+ * LanesPerWalker, RoughFloor, scene props; with a communicator it is local to the rank.
+ *
+ * WK_ERR_ARG, with the text in wk_last_error and nothing launched or written: a NULL pointer,
+ * n_views outside 1..WK_RENDER_MAX_VIEWS, a walker id outside [0, n_env), a dimension outside
+ * 1..WK_RENDER_MAX_DIM, a non-finite or non-positive scale or line_px, a non-finite ox or oy, follow
+ * or joints outside 0..1, a misaligned d_rgba. */
+enum { WK_RENDER_MAX_VIEWS = 4096, WK_RENDER_MAX_DIM = 2048, WK_RENDER_MAX_SEGMENTS = 160 };
+typedef struct wk_render_args {
+  int32_t width, height;  /* pixels, 1..WK_RENDER_MAX_DIM each; default 550 x 325 */
+  float scale;            /* pixels per world unit, finite, > 0; default 0.5 */
+  float ox, oy;           /* world coordinates of the image's top-left corner; default (-50, 400): with
+                             the default frame a window of 1100 x 650 units, the whole flat floor */
+  int32_t follow;         /* 0 (default): ox as given.  1: ox is added to (torso x - 0.5f * ((float)width / scale)) */
+  float line_px;          /* thickness of body outlines in pixels, finite, > 0; default 1; joints and
+                             the marker use 2 * line_px */
+  float marker_x;         /* world x of the vertical Lime marker from y = 500 to y = 900; NaN (default) = none */
+  int32_t joints;         /* 1 (default): draw the joint squares */
+  int32_t pad;
+} wk_render_args;
+void wk_render_defaults(wk_render_args* args); /* no device; a NULL is ignored */
+int wk_render(wk_ctx* ctx, const wk_render_args* args, const int32_t* envs /* host, n_views */, int n_views,
+              uint8_t* rgba /* host, n_views*height*width*4 */);
+int wk_render_device(wk_ctx* ctx, const wk_render_args* args, const int32_t* envs /* HOST */, int n_views,
+                     uint8_t* d_rgba /* device */);
+int wk_render_states(wk_ctx* ctx, const wk_render_args* args, const float* states /* host, n_views*WK_STATE_FLOATS */,
+                     const int32_t* envs /* host */, int n_views, uint8_t* rgba /* host */);
 
 /* Train(Batch) on caller data: B samples, divisor b_div; grads_out (optional, WK_NPARAM)
  * receives the accumulated gradient before Adam. Returns skipped-sample count in *skipped. */

@@ -214,6 +214,36 @@ namespace NEA.Walker
             Wk.Ok(ctx, Wk.wk_evaluate_time(ctx, reps, out var st, out var fo), "Exception while timing the evaluation kernels", log) ? (st, fo) : null;
     }
 
+    // Frames (the counterpart of Environment.RenderObjects, Environment.cs:189-208): the listed
+    // walkers drawn on the device into RGBA bytes [view][row][column][4], row 0 at the top.  Render
+    // draws the context's records as they are, RenderStates host records in wk_get_state's layout
+    // (a saved episode) with the listed walkers' materials, terrain and props.  null on failure, logged
+    public static class Frames
+    {
+        public static WkRenderArgs Defaults()
+        {
+            var a = new WkRenderArgs();
+            Wk.wk_render_defaults(ref a);
+            return a;
+        }
+
+        public static byte[]? Render(IntPtr ctx, WkRenderArgs args, int[] envs, Action<string>? log = null)
+        {
+            var img = new byte[(long)envs.Length * args.Height * args.Width * 4];
+            return Wk.Ok(ctx, Wk.wk_render(ctx, ref args, envs, envs.Length, img), "Exception while rendering", log) ? img : null;
+        }
+
+        public static byte[]? RenderStates(IntPtr ctx, WkRenderArgs args, float[] states, int[] envs, Action<string>? log = null)
+        {
+            var img = new byte[(long)envs.Length * args.Height * args.Width * 4];
+            return Wk.Ok(ctx, Wk.wk_render_states(ctx, ref args, states, envs, envs.Length, img), "Exception while rendering saved states", log) ? img : null;
+        }
+
+        // the same frames into device memory (4-byte aligned) on the context's stream: no copy, no synchronise
+        public static bool RenderDevice(IntPtr ctx, WkRenderArgs args, int[] envs, IntPtr deviceRgba, Action<string>? log = null) =>
+            Wk.Ok(ctx, Wk.wk_render_device(ctx, ref args, envs, envs.Length, deviceRgba), "Exception while rendering to device memory", log);
+    }
+
     // Walker/Walker.cs:49-223 for walker `Index` of a context (a Walker owns no state of its own:
     // its bodies, torques, Collided flags and episode counter live in the context's records)
     public sealed class Walker

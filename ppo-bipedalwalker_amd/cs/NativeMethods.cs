@@ -223,6 +223,21 @@ public struct WkEvalArgs
     public uint RngStep0;   // stochastic: Philox step of every walker's first env-step
 }
 
+// wk_render / wk_render_device / wk_render_states: the frame, the window and what to draw
+// (fill it with wk_render_defaults: 550 x 325 at scale 0.5 from (-50, 400), joints on, no marker)
+[StructLayout(LayoutKind.Sequential)]
+public struct WkRenderArgs
+{
+    public int Width, Height;  // pixels, 1..2048 each
+    public float Scale;        // pixels per world unit
+    public float Ox, Oy;       // world coordinates of the image's top-left corner
+    public int Follow;         // 1 = Ox is added to (torso x - half the window's width)
+    public float Line_px;      // thickness of body outlines in pixels (joints and the marker use twice that)
+    public float Marker_x;     // world x of the vertical Lime marker, NaN = none
+    public int Joints;         // 1 = draw the joint squares
+    public int Pad;
+}
+
 // one episode slot of wk_evaluate, layout [episode][walker], End: 0 fell, 1 time limit, 2 success, 3 unfinished
 [StructLayout(LayoutKind.Sequential)]
 public struct WkEvalRec
@@ -351,6 +366,10 @@ public static class Wk
     [DllImport(Lib)] public static extern int wk_get_scaled_rewards(IntPtr ctx, [Out] float[] rewards);
     [DllImport(Lib)] public static extern int wk_evaluate(IntPtr ctx, ref WkEvalArgs args, out WkEvalStats stats, [Out] WkEvalRec[]? recs);
     [DllImport(Lib)] public static extern int wk_evaluate_time(IntPtr ctx, int reps, out double stepMs, out double foldMs);
+    [DllImport(Lib)] public static extern void wk_render_defaults(ref WkRenderArgs args);
+    [DllImport(Lib)] public static extern int wk_render(IntPtr ctx, ref WkRenderArgs args, int[] envs, int nViews, [Out] byte[] rgba);
+    [DllImport(Lib)] public static extern int wk_render_device(IntPtr ctx, ref WkRenderArgs args, int[] envs, int nViews, IntPtr deviceRgba);
+    [DllImport(Lib)] public static extern int wk_render_states(IntPtr ctx, ref WkRenderArgs args, float[] states, int[] envs, int nViews, [Out] byte[] rgba);
     [DllImport(Lib)] public static extern int wk_train_batch(IntPtr ctx, int B, float bDiv, float[] states, float[] actions, float[] logpOld, float[] returns, float[] adv, out float criticDiag, out float actorDiag, float[]? gradsOut, int applyAdam, out int skipped);
     [DllImport(Lib)] public static extern int wk_minibatch_gradient(IntPtr ctx, int B, float bDiv, float[] states, float[] actions, float[] logpOld, float[] returns, float[] adv, out float criticDiag, out float actorDiag, float[]? gradsOut, out int skipped);
 

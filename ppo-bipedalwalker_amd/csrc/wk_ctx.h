@@ -115,6 +115,11 @@ struct wk_ctx {
     wk::EvalArgs a;  // the running episodes, the records, the running count
     bool valid = false;
   } evb{};
+  // the frame renderer's buffers (wk_render*; grown on demand, kept between calls): the views'
+  // walker ids, wk_render_states' records and the host variants' device image
+  int32_t* rd_envs = nullptr; size_t rd_envs_bytes = 0;
+  float* rd_states = nullptr; size_t rd_states_bytes = 0;
+  uint32_t* rd_img = nullptr; size_t rd_img_bytes = 0;
   // scene props (wk_set_scene): descriptions, kernel constants, [n][pstride] state
   std::vector<wk_prop> scene_desc;
   wk::SceneDev scene{};

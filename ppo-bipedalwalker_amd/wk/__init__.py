@@ -52,6 +52,7 @@ EXPORTS = [
     "wk_get_log_std", "wk_set_log_std", "wk_set_log_std_adam", "wk_log_std_gradient",
     "wk_reward_norm_defaults", "wk_reward_norm_config", "wk_reward_norm_get", "wk_reward_norm_set",
     "wk_reward_norm_get_acc", "wk_reward_norm_set_acc", "wk_reward_norm_update", "wk_get_scaled_rewards",
+    "wk_render_defaults", "wk_render", "wk_render_device", "wk_render_states",
 ]
 
 
@@ -279,6 +280,33 @@ class EvalStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+RENDER_MAX_VIEWS, RENDER_MAX_DIM, RENDER_MAX_SEGMENTS = 4096, 2048, 160  # WK_RENDER_MAX_*
+# the renderer's tile (csrc/wk_render.h): one block of 256 threads per 64 x 16 pixels of one view
+RENDER_TILE_W, RENDER_TILE_H = 64, 16
+
+
+class RenderArgs(C.Structure):
+    """wk_render_args: the frame, the window (scale, origin, follow) and what to draw"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("scale", C.c_float), ("ox", C.c_float),
+                ("oy", C.c_float), ("follow", C.c_int32), ("line_px", C.c_float), ("marker_x", C.c_float),
+                ("joints", C.c_int32), ("pad", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
+def render_args(**args):
+    """wk_render_defaults (550 x 325 at scale 0.5 from (-50, 400), no follow, line_px 1, no marker,
+    joints on) with the given fields replaced"""
+    a = RenderArgs()
+    load_library().wk_render_defaults(C.byref(a))
+    for k, v in args.items():
+        if k == "pad" or k not in dict(RenderArgs._fields_):
+            raise KeyError(f"unknown wk_render_args field {k}")
+        setattr(a, k, v)
+    return a
+
+
 # the statistics kernels' grids (csrc/wk_kernels.h): the built-in kernel runs at most
 # STATS_MAX_BLOCKS blocks of STATS_WAVES waves, each wave striding over the 16-row chunks; the
 # general kernel at most NET_MAX_BLOCKS one-wave blocks of equally many consecutive 16-row tiles
@@ -426,6 +454,10 @@ def load_library(path=None):
         "wk_reward_norm_set_acc": (I, [P, P]),
         "wk_reward_norm_update": (I, [P]),
         "wk_get_scaled_rewards": (I, [P, P]),
+        "wk_render_defaults": (None, [C.POINTER(RenderArgs)]),
+        "wk_render": (I, [P, C.POINTER(RenderArgs), P, I, P]),
+        "wk_render_device": (I, [P, C.POINTER(RenderArgs), P, I, P]),
+        "wk_render_states": (I, [P, C.POINTER(RenderArgs), P, P, I, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -952,6 +984,39 @@ class Engine:
         s, f = C.c_double(), C.c_double()
         self._chk(self.lib.wk_evaluate_time(self.h, int(reps), C.byref(s), C.byref(f)), "wk_evaluate_time")
         return s.value, f.value
+
+    @staticmethod
+    def _views(envs):
+        return np.ascontiguousarray([0] if envs is None else envs, dtype=np.int32).reshape(-1)
+
+    def render(self, envs=None, **args):
+        """wk_render: the listed walkers (None: walker 0; repeats allowed) as they are now, drawn on
+        the device -- floor, bodies in the material's colour, joint squares by torque, props, an
+        optional marker -- as uint8 [n, H, W, 4] RGBA, row 0 at the top.  args: wk_render_args
+        fields (width, height, scale, ox, oy, follow, line_px, marker_x, joints)"""
+        a, ids = render_args(**args), self._views(envs)
+        img = np.empty((ids.size, a.height, a.width, 4), np.uint8)
+        self._chk(self.lib.wk_render(self.h, C.byref(a), _ptr(ids), ids.size, _ptr(img)), "wk_render")
+        return img
+
+    def render_states(self, states, envs, **args):
+        """wk_render_states: host records [n, STATE_FLOATS] (get_state's layout) drawn as if walker
+        envs[i] had record states[i]; material, terrain and props are that walker's"""
+        a, ids = render_args(**args), self._views(envs)
+        st = _f32(states, (ids.size, STATE_FLOATS))
+        img = np.empty((ids.size, a.height, a.width, 4), np.uint8)
+        self._chk(self.lib.wk_render_states(self.h, C.byref(a), _ptr(st), _ptr(ids), ids.size, _ptr(img)),
+                  "wk_render_states")
+        return img
+
+    def render_device(self, ptr, envs, **args):
+        """wk_render_device: the same frames into device memory at `ptr` (an int, for example a torch
+        uint8 tensor's data_ptr(); 4-byte aligned, n * H * W * 4 bytes) on the context's stream; no
+        copy and no synchronise.  Returns the image's shape"""
+        a, ids = render_args(**args), self._views(envs)
+        self._chk(self.lib.wk_render_device(self.h, C.byref(a), _ptr(ids), ids.size, C.c_void_p(int(ptr))),
+                  "wk_render_device")
+        return (ids.size, a.height, a.width, 4)
 
     def ppo_update(self, epochs=0, minibatch=0, minibatch_global=0, update_index=0, sync=True):
         """Whole PPO update; returns the last minibatch's (critic, actor) diagnostics, or
