@@ -118,7 +118,8 @@ typedef struct wk_config {
                                included.  Limits (WK_ERR_CONFIG before a device is touched): per
                                network at most 8 layers (dense and activation together), at
                                most 4 dense layers, every width in 1..128.  The strings are
-                               copied at wk_create.  One GPU: the multi-GPU gradient exchange
+                               copied at wk_create.  One GPU (wk_comm_records refuses such a
+                               context too): the multi-GPU gradient exchange
                                (wk_comm_init, wk_comm_init_host, wk_comm_ipc_handle,
                                wk_comm_init_ipc) returns WK_ERR_CONFIG on such a context.  Not
                                part of the JSON document */
@@ -138,10 +139,13 @@ typedef struct wk_config {
                                synchronise per epoch); when its kl > TargetKL (strict; a NaN never
                                stops) the remaining epochs are not run.  wk_update_stats_get
                                returns the last check.  Negative or non-finite is WK_ERR_CONFIG
-                               before a device is touched.  One GPU: ranks deciding on their own
-                               shards would desert each other mid-exchange, so wk_comm_init,
-                               wk_comm_init_host, wk_comm_ipc_handle and wk_comm_init_ipc return
-                               WK_ERR_CONFIG on such a context.  Not part of the JSON document */
+                               before a device is touched.  One GPU, or any number with
+                               wk_comm_records: ranks deciding on their own shards would desert
+                               each other mid-exchange, so without that call wk_comm_init and
+                               wk_comm_init_host return WK_ERR_CONFIG on such a context (after it
+                               every rank decides on the ranks' summed record);
+                               wk_comm_ipc_handle and wk_comm_init_ipc always do.  Not part of the
+                               JSON document */
   float MaxGradNorm;        /* 0 (default): off -- every minibatch launches what it always did.  > 0:
                                per-network gradient-norm clipping in every Adam step (wk_ppo_update,
                                wk_train_batch with apply_adam).  Critic = parameters [0, n_critic)
@@ -179,8 +183,10 @@ typedef struct wk_config {
                                recorded log-densities stay the old policy's.  With TargetKL > 0
                                the same pass yields that check's record (one pass per epoch; the
                                order is pass, log-std step, stop decision).  MaxGradNorm does not
-                               touch s.  One GPU, like TargetKL: the four wk_comm_* initialisers
-                               return WK_ERR_CONFIG on such a context.  Anything but 0 or 1 is
+                               touch s.  One GPU, or any number with wk_comm_records, like
+                               TargetKL: without that call the wk_comm_* initialisers return
+                               WK_ERR_CONFIG on such a context (after it every rank steps s on the
+                               ranks' summed record).  Anything but 0 or 1 is
                                WK_ERR_CONFIG.  Not part of the JSON document, like the four below */
   float LogStdAlpha;        /* 0 (default): the log-std step uses the context's current Alpha
                                (wk_set_learning_rate).  > 0: its own learning rate.  Negative or
@@ -571,13 +577,38 @@ int wk_ppo_update(wk_ctx* ctx, const wk_ppo_args* args, float* critic_diag, floa
  * without bootstrap values.  The optional outputs receive the per-row fp32 log-densities
  * logp_new[t][e][4] and values values_new[t][e] of every row, skipped rows included.  No state a
  * later call can observe changes: weights, Adam, Philox counters, trajectory, whether the returns
- * count as valid, logs.  With a communicator it reports this rank's shard.
+ * count as valid, logs.  With a communicator it reports this rank's shard
+ * (wk_policy_stats_global: all the ranks').
  * wk_update_stats_get: the record of the last per-epoch check of this context's last
  * wk_ppo_update, with epochs_run and stopped_early; WK_ERR_STATE when that update made no check
  * (TargetKL = 0, or no update yet). */
 int wk_policy_stats(wk_ctx* ctx, wk_ppo_stats* out, float* logp_new /* T*n*4 or NULL */,
                     float* values_new /* T*n or NULL */);
 int wk_update_stats_get(wk_ctx* ctx, wk_ppo_stats* out);
+/* The raw sums behind wk_ppo_stats and wk_log_std_grad: the record the device passes end in and
+ * the host divides, as the record exchange (wk_comm_records) gathers it.
+ * wk_ppo_sums_add: the fold step, acc = acc + x -- integers add, doubles add, rmax is the larger
+ * with a NaN on either side staying.  wk_ppo_stats_from_sums and wk_log_std_grad_from_sums: the
+ * divisions of wk_policy_stats and wk_log_std_gradient (epochs_run and stopped_early 0).  The
+ * three are host arithmetic with no context and no device; NULLs are ignored.
+ * wk_policy_sums: the log-std pass once, with wk_policy_stats' state rules and errors; *local is
+ * this rank's record.  A non-NULL global makes the call COLLECTIVE on a record-exchange context
+ * (every rank makes it): *global is the ranks' records folded in rank order, the same bytes on
+ * every rank.  A context with no communicator returns the local record as the global one; a
+ * communicator without wk_comm_records is WK_ERR_STATE.  wk_policy_stats_global:
+ * wk_ppo_stats_from_sums of that global record. */
+typedef struct wk_ppo_sums {
+  int64_t rows, skipped, clipped;  /* counted rows, skipped rows, clipped (row, dimension) entries */
+  double kl, k1, surr;             /* over counted entries: expm1(d) - d, -d, the clipped surrogate */
+  double sr, srr, se, see;         /* over counted rows: ret, ret^2, e = ret - V, e^2 */
+  double rmax;                     /* largest ratio (-inf: none; a NaN stays) */
+  double term, zz;                 /* the log-std pass's two sums: w (zz - 1) and zz */
+} wk_ppo_sums;
+void wk_ppo_sums_add(wk_ppo_sums* acc, const wk_ppo_sums* x);
+void wk_ppo_stats_from_sums(const wk_ppo_sums* s, wk_ppo_stats* out);
+void wk_log_std_grad_from_sums(const wk_ppo_sums* s, float entropy_coef, wk_log_std_grad* out);
+int wk_policy_sums(wk_ctx* ctx, wk_ppo_sums* local, wk_ppo_sums* global_or_null);
+int wk_policy_stats_global(wk_ctx* ctx, wk_ppo_stats* out);
 /* wk_grad_norms_get: the gradient-norm record of the last wk_ppo_update / wk_train_batch of a
  * MaxGradNorm > 0 context.  It synchronises the stream (wk_ppo_update itself stays asynchronous).
  * WK_ERR_STATE on a MaxGradNorm = 0 context, or when no Adam step ran since the record was last
@@ -642,9 +673,19 @@ int wk_log_std_gradient(wk_ctx* ctx, wk_log_std_grad* out);
  * wk_reward_norm_config: NaNs, clip <= 0, a negative or non-finite epsilon, enable or frozen outside
  * 0..1 are WK_ERR_ARG and change nothing.  The first enable allocates and zeroes the state; a
  * disable keeps it for a later enable.  Every change marks the returns stale and, with a trajectory
- * in the buffer, re-runs the apply step.  WK_ERR_CONFIG when enabling on a context with a
- * communicator, and from the four wk_comm_* initialisers on an enabled context (every rank would
- * scale by its own shard's statistics).
+ * in the buffer, re-runs the apply step.  One GPU, or any number with wk_comm_records: without
+ * that call it is WK_ERR_CONFIG to enable on a context with a communicator, and the wk_comm_*
+ * initialisers return it on an enabled context (every rank would scale by its own shard's
+ * statistics).  On a record-exchange context (wk_comm_records, then wk_comm_init or
+ * wk_comm_init_host) the finish step is split: every rank's batch record (count, non-finite, sum x,
+ * sum x^2) is gathered, every rank folds the records in rank order and merges the fold, so all
+ * ranks end the pass with the same (count, mean, m2, var, scale) bytes, `nonfinite` counts all
+ * ranks' samples, and rows / clipped / acc stay this rank's.  wk_rollout and wk_reward_norm_update
+ * are then COLLECTIVE calls (every rank makes them, in the same order); on an RCCL context
+ * wk_rollout stays asynchronous and a header mismatch of its exchange is reported by the next
+ * wk_sync, wk_reward_norm_get, wk_get_scaled_rewards, wk_policy_sums or wk_ppo_update.  A frozen
+ * pass, wk_set_trajectory's apply step, wk_reward_norm_set and wk_reward_norm_set_acc exchange
+ * nothing: the caller sets them alike on every rank.
  * frozen = 1 makes every pass the apply step alone.  wk_set_trajectory on an enabled context runs
  * the apply step alone with the current scale (foreign data: nothing is learned from it); a host
  * that wants it learned calls wk_reward_norm_update once afterwards (twice counts the data twice).
@@ -872,6 +913,37 @@ int wk_write_data_file(const char* path, const float* total_rewards, int64_t n_r
 
 /* multi-GPU: RCCL communicator over the ranks' contexts (one per GPU) */
 int wk_comm_unique_id(uint8_t* id /* 128 bytes */);
+/* The record exchange: TargetKL, LearnLogStd and reward normalisation on any number of GPUs.
+ * wk_comm_records, called before the gradient exchange is initialised, declares that this
+ * context's ranks will exchange their statistics records.  fn NULL: RCCL (ncclAllGather of the
+ * WK_COMM_RECORD_WORDS words on the context's stream), valid only when followed by wk_comm_init;
+ * otherwise the host control plane, valid only when followed by wk_comm_init_host: fn receives
+ * this rank's record and must fill `all` with every rank's, in rank order (return 0).  It is the
+ * counterpart of wk_host_allreduce_fn and is kept for the context's lifetime.  After the call the
+ * matching initialiser accepts a context with TargetKL > 0, LearnLogStd = 1 or reward
+ * normalisation enabled, and wk_reward_norm_config may enable once the communicator exists.
+ * Without the call nothing changes.  WK_ERR_STATE after any wk_comm_* initialiser, for a second
+ * call, and from an initialiser that does not match the declared kind; WK_ERR_CONFIG on a
+ * NetworkKernels = 1 context.  The IPC exchange stays closed: wk_comm_ipc_handle and
+ * wk_comm_init_ipc return WK_ERR_CONFIG on such contexts with or without the call (they fuse
+ * reduction, exchange and Adam in one launch).
+ * Records are gathered, not summed in flight: every rank receives every rank's record byte for
+ * byte and folds them itself in rank order starting from rank 0's, so all ranks decide on the
+ * same bytes (with one rank the fold is the identity).  Word 0 of a record is its header, kind <<
+ * 56 | nranks << 48 | sequence (kind 1 statistics, 2 reward normalisation; sequence this context's
+ * count of record exchanges); a rank whose header differs from the caller's, a non-zero return of
+ * fn or a failed ncclAllGather is WK_ERR_COMM naming the first differing rank, fatal for the job
+ * like a failed all-reduce, and no step is taken.
+ * On such a context, once the communicator exists: wk_ppo_update gathers one record per epoch
+ * (TargetKL > 0 or LearnLogStd = 1) and takes the log-std step and the stop decision from the
+ * fold, which wk_update_stats_get and wk_get_log_std's grad_last then report; wk_rollout and
+ * wk_reward_norm_update gather the batch record of the reward normalisation (see there).
+ * NormalizeAdvantages, wk_policy_stats, wk_log_std_gradient, wk_rollout_stats_get and wk_evaluate
+ * stay this rank's shard. */
+enum { WK_COMM_RECORD_WORDS = 16 };            /* one record: 16 64-bit words */
+typedef int wk_host_allgather_fn(const uint64_t* mine /* 16 */, uint64_t* all /* nranks*16, rank order */,
+                                 void* user);
+int wk_comm_records(wk_ctx* ctx, wk_host_allgather_fn* fn_or_null, void* user);
 int wk_comm_init(wk_ctx* ctx, int rank, int nranks, const uint8_t* unique_id);
 /* sum of host_buf over the ranks, in place, through the context's exchange: RCCL, or with
  * wk_comm_init_ipc one round of the IPC exchange (n <= 6,152 floats; ranks summed in rank order;

@@ -120,6 +120,28 @@ namespace NEA.Walker
 
         public static WkPpoStats? LastUpdate(IntPtr ctx, Action<string>? log = null) =>
             Wk.Ok(ctx, Wk.wk_update_stats_get(ctx, out var s), "Exception while reading the update's statistics", log) ? s : null;
+
+        // over all the ranks' shards: collective on a record-exchange context (RecordExchange.Declare)
+        public static WkPpoStats? Global(IntPtr ctx, Action<string>? log = null) =>
+            Wk.Ok(ctx, Wk.wk_policy_stats_global(ctx, out var s), "Exception while reading the global policy statistics", log) ? s : null;
+
+        // this rank's raw sums, as the record exchange gathers them
+        public static WkPpoSums? Sums(IntPtr ctx, Action<string>? log = null) =>
+            Wk.Ok(ctx, Wk.wk_policy_sums(ctx, out var s, IntPtr.Zero), "Exception while reading the policy sums", log) ? s : null;
+
+        public static WkPpoSums Add(WkPpoSums acc, WkPpoSums x) { Wk.wk_ppo_sums_add(ref acc, ref x); return acc; }
+        public static WkPpoStats FromSums(WkPpoSums sums) { Wk.wk_ppo_stats_from_sums(ref sums, out var s); return s; }
+        public static WkLogStdGrad LogStdGradFromSums(WkPpoSums sums, float entropyCoef) { Wk.wk_log_std_grad_from_sums(ref sums, entropyCoef, out var g); return g; }
+    }
+
+    // TargetKL, LearnLogStd and reward normalisation on several GPUs: declared before the gradient
+    // exchange is initialised, the ranks then gather their statistics records and every rank decides
+    // on the same fold.  gather null: RCCL (then wk_comm_init); else the host control plane (then
+    // Wk.CommInitHost)
+    public static class RecordExchange
+    {
+        public static bool Declare(IntPtr ctx, Wk.HostAllGather? gather = null, Action<string>? log = null) =>
+            Wk.Ok(ctx, Wk.CommRecords(ctx, gather, IntPtr.Zero), "Exception while declaring the record exchange", log);
     }
 
     // The size of the optimiser's steps (no counterpart in the reference): the per-network gradient

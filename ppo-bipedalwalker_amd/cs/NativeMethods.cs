@@ -173,6 +173,15 @@ public unsafe struct WkGradNorms
     public fixed int Pad[2];
 }
 
+// wk_policy_sums: the raw sums the statistics passes end in, as the record exchange (wk_comm_records) gathers them
+[StructLayout(LayoutKind.Sequential)]
+public struct WkPpoSums
+{
+    public long Rows, Skipped, Clipped;
+    public double Kl, K1, Surr, Sr, Srr, Se, See, Rmax;
+    public double Term, Zz;
+}
+
 // wk_log_std_gradient: the clipped surrogate's derivative by the scalar log-std over the trajectory buffer, host-divided
 [StructLayout(LayoutKind.Sequential)]
 public struct WkLogStdGrad
@@ -349,6 +358,12 @@ public static class Wk
     [DllImport(Lib)] public static extern int wk_ppo_update(IntPtr ctx, ref WkPpoArgs args, out float criticDiag, out float actorDiag);
     [DllImport(Lib)] public static extern int wk_policy_stats(IntPtr ctx, out WkPpoStats stats, float[]? logpNew, float[]? valuesNew);
     [DllImport(Lib)] public static extern int wk_update_stats_get(IntPtr ctx, out WkPpoStats stats);
+    [DllImport(Lib)] public static extern void wk_ppo_sums_add(ref WkPpoSums acc, ref WkPpoSums x);
+    [DllImport(Lib)] public static extern void wk_ppo_stats_from_sums(ref WkPpoSums sums, out WkPpoStats stats);
+    [DllImport(Lib)] public static extern void wk_log_std_grad_from_sums(ref WkPpoSums sums, float entropyCoef, out WkLogStdGrad grad);
+    // global: IntPtr.Zero for this rank's record alone; else a WkPpoSums' address (collective on a record-exchange context)
+    [DllImport(Lib)] public static extern int wk_policy_sums(IntPtr ctx, out WkPpoSums local, IntPtr globalOrNull);
+    [DllImport(Lib)] public static extern int wk_policy_stats_global(IntPtr ctx, out WkPpoStats stats);
     [DllImport(Lib)] public static extern int wk_grad_norms_get(IntPtr ctx, out WkGradNorms norms);
     [DllImport(Lib)] public static extern int wk_set_learning_rate(IntPtr ctx, float alpha);
     [DllImport(Lib)] public static extern int wk_get_learning_rate(IntPtr ctx, out float alpha);
@@ -393,6 +408,19 @@ public static class Wk
     [UnmanagedFunctionPointer(CallingConvention.Cdecl)] public delegate int HostAllReduce(IntPtr buf, int n, IntPtr user);
     [DllImport(Lib)] public static extern int wk_comm_init_host(IntPtr ctx, int rank, int nRanks, HostAllReduce fn, IntPtr user);
 
+    // The record exchange (before wk_comm_init / wk_comm_init_host): fn is IntPtr.Zero for RCCL, else the function pointer
+    // of a HostAllGather (mine: 16 words in, all: nRanks * 16 words out, rank order).  Use CommRecords, which keeps the
+    // delegate reachable for the context's lifetime as CommInitHost does.
+    [UnmanagedFunctionPointer(CallingConvention.Cdecl)] public delegate int HostAllGather(IntPtr mine, IntPtr all, IntPtr user);
+    [DllImport(Lib)] public static extern int wk_comm_records(IntPtr ctx, IntPtr fnOrNull, IntPtr user);
+    static readonly System.Collections.Concurrent.ConcurrentDictionary<IntPtr, HostAllGather> s_hostAllGather = new();
+    public static int CommRecords(IntPtr ctx, HostAllGather? fn, IntPtr user)
+    {
+        int rc = wk_comm_records(ctx, fn == null ? IntPtr.Zero : Marshal.GetFunctionPointerForDelegate(fn), user);
+        if (rc == 0 && fn != null) s_hostAllGather[ctx] = fn;
+        return rc;
+    }
+
     // libwk keeps the function pointer for the context's lifetime; the marshalled thunk dies with
     // the delegate, so the delegate must stay reachable until the context is destroyed.  Use
     // CommInitHost / Destroy instead of the raw entry points when a host all-reduce is set.
@@ -409,6 +437,7 @@ public static class Wk
     {
         int rc = wk_destroy(ctx);
         s_hostAllReduce.TryRemove(ctx, out _);
+        s_hostAllGather.TryRemove(ctx, out _);
         return rc;
     }
 

@@ -193,6 +193,26 @@ class PPOAgent {
       LogError(std::string("Exception while reading the policy statistics: ") + wk_last_error(ctx_));
     return s;
   }
+  // The record exchange (before the gradient exchange is initialised): TargetKL, LearnLogStd and
+  // reward normalisation on several GPUs.  gather null: RCCL, else the host control plane's
+  // all-gather.  PolicySums: this rank's raw sums and, with global, the ranks' fold (collective)
+  bool CommRecords(wk_host_allgather_fn* gather = nullptr, void* user = nullptr) {
+    if (wk_comm_records(ctx_, gather, user) == WK_OK) return true;
+    LogError(std::string("Exception while declaring the record exchange: ") + wk_last_error(ctx_));
+    return false;
+  }
+  wk_ppo_sums PolicySums(wk_ppo_sums* global = nullptr) {
+    wk_ppo_sums s{};
+    if (wk_policy_sums(ctx_, &s, global) != WK_OK)
+      LogError(std::string("Exception while reading the policy sums: ") + wk_last_error(ctx_));
+    return s;
+  }
+  wk_ppo_stats PolicyStatisticsGlobal() {
+    wk_ppo_stats s{};
+    if (wk_policy_stats_global(ctx_, &s) != WK_OK)
+      LogError(std::string("Exception while reading the global policy statistics: ") + wk_last_error(ctx_));
+    return s;
+  }
   wk_ppo_stats UpdateStatistics() {
     wk_ppo_stats s{};
     if (wk_update_stats_get(ctx_, &s) != WK_OK)

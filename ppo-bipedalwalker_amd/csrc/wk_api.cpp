@@ -402,6 +402,7 @@ int wk_destroy(wk_ctx* c) {
 int wk_sync(wk_ctx* c) {
   DevGuard dg_(c);
   if (!c) return WK_ERR_ARG;
+  if (int r = rx_deferred(c)) return r;  // (an RCCL wk_rollout's record exchange: reported here)
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return WK_OK;
 }

@@ -1,6 +1,7 @@
 // wk_api_comm.cpp -- the multi-GPU gradient exchange: which contexts it refuses, the RCCL
 // communicator, the host all-reduce callback, the IPC region over peer-mapped memory and its
-// status, and the exchange leg of a minibatch.  The only host unit that sees rccl.h.
+// status, the exchange leg of a minibatch, and the record exchange (wk_comm_records): the gather of
+// the ranks' statistics records and its header check.  The only host unit that sees rccl.h.
 #include <rccl/rccl.h>
 
 #include <cstdlib>
@@ -9,7 +10,10 @@
 #include "wk_ctx.h"
 #include "wk_text.h"
 
-static int refuse_comm(wk_ctx* c) {
+// records: the initialiser serves the record exchange and the context declared it
+// (wk_comm_records), so every rank decides on the ranks' summed statistics
+static int refuse_comm(wk_ctx* c, bool records = false) {
+  if (records && c->rx_kind != wk_ctx::RX_NONE) return WK_OK;  // (never a general context)
   // ranks scaling their rewards by their own shards' statistics would train on different targets
   if (c->rn_on) {
     SETERR(c, "the multi-GPU gradient exchange refuses a context with reward normalisation enabled: "
@@ -119,6 +123,124 @@ void comm_close(wk_ctx* c) {
   if (c->xch) (void)hipFree(c->xch);
 }
 
+// ---------------- the record exchange ----------------
+static_assert(WK_COMM_RECORD_WORDS == wk::RECORD_WORDS, "record width");
+
+int wk_comm_records(wk_ctx* c, wk_host_allgather_fn* fn, void* user) {
+  if (!c) return WK_ERR_ARG;
+  if (c->general) {
+    SETERR(c, "wk_comm_records: the record exchange serves the built-in kernels only (NetworkKernels = 0)");
+    return WK_ERR_CONFIG;
+  }
+  if (c->comm || c->host_ar || c->ipc || c->xch) {
+    SETERR(c, "wk_comm_records comes before the gradient exchange is initialised");
+    return WK_ERR_STATE;
+  }
+  if (c->rx_kind != wk_ctx::RX_NONE) { SETERR(c, "wk_comm_records was already called on this context"); return WK_ERR_STATE; }
+  c->rx_kind = fn ? wk_ctx::RX_HOST : wk_ctx::RX_RCCL;
+  c->rx_fn = fn;
+  c->rx_user = user;
+  return WK_OK;
+}
+
+// the initialiser `kind` against the declared record exchange
+static int rx_match(wk_ctx* c, int kind) {
+  if (c->rx_kind == wk_ctx::RX_NONE || c->rx_kind == kind) return WK_OK;
+  SETERR(c, "wk_comm_records declared %s: initialise the gradient exchange with %s",
+         c->rx_kind == wk_ctx::RX_RCCL ? "the RCCL record exchange" : "a host record exchange",
+         c->rx_kind == wk_ctx::RX_RCCL ? "wk_comm_init" : "wk_comm_init_host");
+  return WK_ERR_STATE;
+}
+
+// the gather buffer and the error word, once the number of ranks is known
+static int rx_alloc(wk_ctx* c, int nranks) {
+  if (c->rx_kind == wk_ctx::RX_NONE) return WK_OK;
+  const size_t bytes = sizeof(uint64_t) * wk::RECORD_WORDS * (size_t)nranks;
+  HIPCHK(c, dev_alloc(c, &c->rx_dev, bytes));
+  HIPCHK(c, hipMemset(c->rx_dev, 0, bytes));
+  HIPCHK(c, dev_alloc(c, &c->rx_err, sizeof(uint32_t)));
+  HIPCHK(c, hipMemset(c->rx_err, 0, sizeof(uint32_t)));
+  c->rx_host.assign((size_t)wk::RECORD_WORDS * nranks, 0);
+  return WK_OK;
+}
+
+uint64_t rx_header(wk_ctx* c, int kind) {
+  const uint64_t seq = c->rx_seq++ & ((1ull << 48) - 1);
+  return ((uint64_t)kind << 56) | ((uint64_t)(c->nranks & 0xff) << 48) | seq;
+}
+
+static int rx_fail(wk_ctx* c, int rank, uint64_t got, uint64_t want) {
+  SETERR(c, "record exchange: rank %d's record has header %016llx where this rank (%d) has %016llx "
+            "(kind << 56 | nranks << 48 | sequence): the ranks' calls are out of step -- fatal for the "
+            "job, abort every rank", rank, (unsigned long long)got, c->rank, (unsigned long long)want);
+  return WK_ERR_COMM;
+}
+
+// every gathered header against this rank's own
+static int rx_check(wk_ctx* c, uint64_t header) {
+  for (int r = 0; r < c->nranks; r++) {
+    const uint64_t h = c->rx_host[(size_t)r * wk::RECORD_WORDS];
+    if (h != header) return rx_fail(c, r, h, header);
+  }
+  return WK_OK;
+}
+
+int rx_deferred(wk_ctx* c) {
+  if (!c->rx_pending) return WK_OK;
+  uint32_t err = 0;
+  HIPCHK(c, hipMemcpyAsync(&err, c->rx_err, sizeof err, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->rx_pending = false;
+  if (!err) return WK_OK;
+  SETERR(c, "record exchange (reward normalisation): rank %u's record carried another header than this "
+            "rank's (%d): the ranks' calls are out of step, nothing was merged -- fatal for the job, "
+            "abort every rank", err - 1u, c->rank);
+  return WK_ERR_COMM;
+}
+
+// the host control plane: this rank's slot out, the caller's all-gather, the headers checked
+static int rx_host_round(wk_ctx* c, uint64_t header) {
+  uint64_t mine[wk::RECORD_WORDS];
+  HIPCHK(c, hipMemcpyAsync(mine, c->rx_dev + (size_t)c->rank * wk::RECORD_WORDS, sizeof mine,
+                           hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::fill(c->rx_host.begin(), c->rx_host.end(), 0);
+  if (c->rx_fn(mine, c->rx_host.data(), c->rx_user) != 0) {
+    SETERR(c, "host record all-gather callback failed");
+    return WK_ERR_COMM;
+  }
+  return rx_check(c, header);
+}
+
+static int rx_nccl_gather(wk_ctx* c) {
+  ncclResult_t r = ncclAllGather(c->rx_dev + (size_t)c->rank * wk::RECORD_WORDS, c->rx_dev,
+                                 wk::RECORD_WORDS, ncclUint64, c->comm, c->stream);
+  if (r != ncclSuccess) { SETERR(c, "ncclAllGather: %s", ncclGetErrorString(r)); return WK_ERR_COMM; }
+  return WK_OK;
+}
+
+int rx_gather_device(wk_ctx* c, uint64_t header) {
+  if (c->comm) {  // stream-ordered: the consumer kernel checks the headers (rx_deferred reports)
+    if (int r = rx_nccl_gather(c)) return r;
+    c->rx_pending = true;
+    return WK_OK;
+  }
+  if (int r = rx_host_round(c, header)) return r;
+  HIPCHK(c, hipMemcpyAsync(c->rx_dev, c->rx_host.data(), sizeof(uint64_t) * c->rx_host.size(),
+                           hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // the host buffer is reused by the next exchange
+  return WK_OK;
+}
+
+int rx_gather_host(wk_ctx* c, uint64_t header) {
+  if (!c->comm) return rx_host_round(c, header);
+  if (int r = rx_nccl_gather(c)) return r;
+  HIPCHK(c, hipMemcpyAsync(c->rx_host.data(), c->rx_dev, sizeof(uint64_t) * c->rx_host.size(),
+                           hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return rx_check(c, header);
+}
+
 int wk_comm_unique_id(uint8_t* id) {
   if (!id) return WK_ERR_ARG;
   static_assert(sizeof(ncclUniqueId) == 128, "nccl id size");
@@ -132,7 +254,9 @@ int wk_comm_unique_id(uint8_t* id) {
 int wk_comm_init(wk_ctx* c, int rank, int nranks, const uint8_t* id) {
   DevGuard dg_(c);
   if (!c || !id || nranks <= 0 || rank < 0 || rank >= nranks) return WK_ERR_ARG;
-  if (int r = refuse_comm(c)) return r;
+  if (int r = rx_match(c, wk_ctx::RX_RCCL)) return r;
+  if (int r = refuse_comm(c, true)) return r;
+  if (c->rx_kind && nranks > 255) { SETERR(c, "the record exchange spans at most 255 ranks"); return WK_ERR_ARG; }
   if (c->host_ar) { SETERR(c, "the context already has a host all-reduce"); return WK_ERR_STATE; }
   HIPCHK(c, hipSetDevice(c->device));
   ncclUniqueId u;
@@ -141,14 +265,17 @@ int wk_comm_init(wk_ctx* c, int rank, int nranks, const uint8_t* id) {
   if (r != ncclSuccess) { SETERR(c, "ncclCommInitRank: %s", ncclGetErrorString(r)); c->comm = nullptr; return WK_ERR_COMM; }
   c->rank = rank;
   c->nranks = nranks;
-  return WK_OK;
+  return rx_alloc(c, nranks);
 }
 
 int wk_comm_init_host(wk_ctx* c, int rank, int nranks, wk_host_allreduce_fn fn, void* user) {
   DevGuard dg_(c);
   if (!c || !fn || nranks <= 0 || rank < 0 || rank >= nranks) return WK_ERR_ARG;
-  if (int r = refuse_comm(c)) return r;
+  if (int r = rx_match(c, wk_ctx::RX_HOST)) return r;
+  if (int r = refuse_comm(c, true)) return r;
+  if (c->rx_kind && nranks > 255) { SETERR(c, "the record exchange spans at most 255 ranks"); return WK_ERR_ARG; }
   if (c->comm) { SETERR(c, "the context already has an RCCL communicator"); return WK_ERR_STATE; }
+  if (int r = rx_alloc(c, nranks)) return r;
   c->host_ar = fn;
   c->host_ar_user = user;
   c->rank = rank;
@@ -166,6 +293,7 @@ int wk_comm_ipc_handle(wk_ctx* c, uint8_t* handle) {
   if (!c || !handle) return WK_ERR_ARG;
   if (int r = refuse_comm(c)) return r;
   if (int r = refuse_ipc_clip(c)) return r;
+  if (int r = rx_match(c, -1)) return r;  // (the IPC exchange carries no records)
   if (!c->xch) {
     // uncached (MTYPE UC) device memory: the peers read it over xGMI and this GPU writes it
     // through no cache; coarse-grained hipMalloc memory is the fallback where the driver cannot
@@ -200,6 +328,7 @@ int wk_comm_init_ipc(wk_ctx* c, int rank, int nranks, const uint8_t* handles) {
   if (!c || !handles || nranks <= 0 || rank < 0 || rank >= nranks) return WK_ERR_ARG;
   if (int r = refuse_comm(c)) return r;
   if (int r = refuse_ipc_clip(c)) return r;
+  if (int r = rx_match(c, -1)) return r;  // (the IPC exchange carries no records)
   if (nranks > wk::XCH_MAX_RANKS) { SETERR(c, "the IPC exchange spans at most %d ranks", (int)wk::XCH_MAX_RANKS); return WK_ERR_ARG; }
   if (c->comm || c->host_ar || c->ipc) { SETERR(c, "the context already has an all-reduce"); return WK_ERR_STATE; }
   if (!c->xch) { SETERR(c, "wk_comm_ipc_handle first"); return WK_ERR_STATE; }

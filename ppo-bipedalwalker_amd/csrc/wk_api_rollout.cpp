@@ -61,8 +61,20 @@ static int bootstrap_values(wk_ctx* c) {
 // learn: the full pass -- the scan carries rn_acc, the finish step merges the batch into rn_rec and
 // forms the scale, the apply step writes trs; otherwise, and on a frozen context, the apply step
 // alone with the scale as it is.
+// On a record-exchange context the full pass is collective: scan and this rank's batch record, the
+// gather of the ranks' records (RCCL: on the stream, no wait; host: through the callback), then the
+// rank-ordered fold, the merge and the apply step -- the same statistics bytes on every rank.
 static int rnorm_pass(wk_ctx* c, bool learn) {
   ProfScope ps(c, PK_RET);
+  if (learn && !c->rn_frozen && records_on(c)) {
+    const uint64_t header = rx_header(c, 2);
+    HIPCHK(c, wk::launch_rnorm_batch(c->n, c->T_valid, c->cfg.Gamma, c->tr, c->td, c->rn_acc, c->rn_partial,
+                                     header, c->rx_dev + (size_t)c->rank * wk::RECORD_WORDS, c->stream));
+    if (int r = rx_gather_device(c, header)) return r;
+    HIPCHK(c, wk::launch_rnorm_merge(c->n, c->T_valid, c->rn_clip, c->rn_eps, c->rx_dev, c->nranks, header,
+                                     c->rx_err, c->tr, c->rn_rec, c->trs, c->stream));
+    return WK_OK;
+  }
   HIPCHK(c, wk::launch_rnorm_pass(c->n, c->T_valid, c->cfg.Gamma, c->rn_clip, c->rn_eps,
                                   learn && !c->rn_frozen, c->tr, c->td, c->rn_acc, c->rn_partial,
                                   c->rn_rec, c->trs, c->stream));
@@ -237,9 +249,9 @@ int wk_reward_norm_config(wk_ctx* c, const wk_reward_norm_args* a) {
               "finite and >= 0 (got %d, %d, %g, %g)", a->enable, a->frozen, (double)a->clip, (double)a->epsilon);
     return WK_ERR_ARG;
   }
-  if (a->enable && (c->comm || c->host_ar || c->ipc || c->xch)) {
-    SETERR(c, "reward normalisation is one GPU: this context has a gradient exchange, and every rank "
-              "would scale by its own shard's statistics");
+  if (a->enable && (c->comm || c->host_ar || c->ipc || c->xch) && !records_on(c)) {
+    SETERR(c, "reward normalisation is one GPU without wk_comm_records: this context has a gradient "
+              "exchange, and every rank would scale by its own shard's statistics");
     return WK_ERR_CONFIG;
   }
   if (a->enable && !c->rn_ever) {  // the first enable: acc 0, no samples, scale 1
@@ -279,6 +291,7 @@ int wk_reward_norm_get(wk_ctx* c, wk_reward_norm* out) {
   memset(out, 0, sizeof(*out));
   out->scale = 1.0f;
   if (!c->rn_ever) return WK_OK;
+  if (int r = rx_deferred(c)) return r;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(out, c->rn_rec, sizeof(*out), hipMemcpyDeviceToHost));
   out->clip = c->rn_clip;
@@ -341,6 +354,7 @@ int wk_get_scaled_rewards(wk_ctx* c, float* out) {
   if (!c || !out) return WK_ERR_ARG;
   if (int r = rnorm_need(c, "wk_get_scaled_rewards")) return r;
   if (c->T_valid <= 0) { SETERR(c, "wk_get_scaled_rewards: no trajectory recorded"); return WK_ERR_STATE; }
+  if (int r = rx_deferred(c)) return r;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(out, c->trs, sizeof(float) * c->n * c->T_valid, hipMemcpyDeviceToHost));
   return WK_OK;

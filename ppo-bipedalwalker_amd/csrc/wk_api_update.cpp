@@ -161,37 +161,23 @@ static hipError_t launch_stats_for(wk_ctx* c, const wk::StatsArgs& a, int nblock
                     : wk::launch_ppo_stats(a, nblocks, log_std, c->stream);
 }
 
-// wk_ppo_stats from the device's record: the host divides
-static void stats_from_rec(const wk::StatsRec& r, wk_ppo_stats* o) {
-  const double nan = std::numeric_limits<double>::quiet_NaN();
-  memset(o, 0, sizeof(*o));
-  o->samples = r.rows;
-  o->skipped = r.skipped;
-  const double n = (double)r.rows, ne = 4.0 * n;  // (0 / 0: every mean of no rows is NaN)
-  o->kl = r.kl / ne;
-  o->kl_k1 = r.k1 / ne;
-  o->clip_fraction = (double)r.clipped / ne;
-  o->ratio_max = r.rows > 0 ? r.rmax : nan;
-  o->surrogate = r.surr / ne;
-  o->value_loss = r.see / n;
-  // population variances from the sums; a Var(ret) within the rounding of its own sums (n terms
-  // of srr, each to 2^-53) is the variance of a constant: 0
-  const double mr = r.sr / n, me = r.se / n;
-  const double var_r = r.srr / n - mr * mr, var_e = r.see / n - me * me;
-  const bool flat = var_r <= 4.0 * n * 0x1p-53 * (r.srr / n);
-  o->explained_variance = (r.rows > 0 && !flat) ? 1.0 - var_e / var_r : nan;
-  if (var_r != var_r) o->explained_variance = nan;
-}
+static_assert(sizeof(wk_ppo_sums) == sizeof(wk::StatsRecLS) && sizeof(wk_ppo_sums) == 8 * wk::STATS_FIELDS_LS &&
+              8 * wk::STATS_FIELDS_LS < 8 * wk::RECORD_WORDS, "wk_ppo_sums is StatsRecLS, and fits a record");
 
 // The statistics pass over the valid trajectory buffer with the current weights (wk_policy_stats
 // and the per-epoch check of a TargetKL > 0 update): forward kernel, k_stats_finish, the record
 // and the optional per-row outputs copied to the host.  Stale returns are computed first, and
 // whether they count as valid is left as it was.
-// ls: the log-std pass instead (wk_log_std_gradient, the LearnLogStd step) -- the kernels' wide
-// instantiation, whose record holds the statistics' record too; out may then be null.
-static int stats_impl(wk_ctx* c, wk_ppo_stats* out, float* logp_new, float* values_new,
-                      wk_log_std_grad* ls = nullptr) {
+// wide: the log-std pass instead (wk_log_std_gradient, the LearnLogStd step) -- the kernels' wide
+// instantiation, whose record holds the statistics' record too (the narrow pass leaves term and zz 0).
+// global: on a record-exchange context (records_on) the pass is collective -- this rank's record
+// goes through the gather behind a header, and *global is the ranks' records folded in rank order
+// from rank 0's; the copy to the host the pass makes anyway is the gathered records'.
+static int sums_impl(wk_ctx* c, bool wide, wk_ppo_sums* local, wk_ppo_sums* global, float* logp_new,
+                     float* values_new) {
   if (c->T_valid <= 0) { SETERR(c, "wk_policy_stats before wk_rollout / wk_set_trajectory"); return WK_ERR_STATE; }
+  if (global)
+    if (int r = rx_deferred(c)) return r;
   if (!c->returns_valid) {
     int r = returns_impl(c);
     if (r) return r;
@@ -205,7 +191,6 @@ static int stats_impl(wk_ctx* c, wk_ppo_stats* out, float* logp_new, float* valu
   a.g.states = c->ts; a.g.actions = c->ta; a.g.logp_old = c->tlp; a.g.returns = c->tret; a.g.adv = c->tadv;
   a.g.pool = (uint32_t)rows;
   a.g.samples = (int)rows;
-  const bool wide = ls != nullptr;
   const size_t rec_bytes = wide ? sizeof(wk::StatsRecLS) : sizeof(wk::StatsRec);
   void* d_rec;
   if (carve(c, &c->scratch2, &c->scratch2_bytes,
@@ -215,23 +200,63 @@ static int stats_impl(wk_ctx* c, wk_ppo_stats* out, float* logp_new, float* valu
     return WK_ERR_HIP;
   HIPCHK(c, launch_stats_for(c, a, nblocks, wide));
   HIPCHK(c, wk::launch_stats_finish(a.partial, nblocks, wide, d_rec, c->stream));
-  wk::StatsRecLS recw{};
-  wk::StatsRec& rec = recw.s;  // (the wide record starts with the statistics' record)
-  HIPCHK(c, hipMemcpyAsync(&recw, d_rec, rec_bytes, hipMemcpyDeviceToHost, c->stream));
+  memset(local, 0, sizeof(*local));
+  if (global) {
+    const uint64_t header = rx_header(c, 1);
+    HIPCHK(c, wk::launch_record_pack(d_rec, (int)(rec_bytes / 8), header,
+                                     c->rx_dev + (size_t)c->rank * wk::RECORD_WORDS, c->stream));
+    if (int r = rx_gather_host(c, header)) return r;
+    const auto rec_of = [&](int r) {
+      wk_ppo_sums x;
+      memcpy(&x, c->rx_host.data() + (size_t)r * wk::RECORD_WORDS + 1, sizeof x);
+      return x;
+    };
+    *local = rec_of(c->rank);
+    *global = rec_of(0);
+    for (int r = 1; r < c->nranks; r++) {
+      const wk_ppo_sums x = rec_of(r);
+      wk_ppo_sums_add(global, &x);
+    }
+    return WK_OK;
+  }
+  HIPCHK(c, hipMemcpyAsync(local, d_rec, rec_bytes, hipMemcpyDeviceToHost, c->stream));
   if (logp_new)
     HIPCHK(c, hipMemcpyAsync(logp_new, a.logp_new, sizeof(float) * 4 * rows, hipMemcpyDeviceToHost, c->stream));
   if (values_new)
     HIPCHK(c, hipMemcpyAsync(values_new, a.values_new, sizeof(float) * rows, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (out) stats_from_rec(rec, out);
-  if (ls) {  // the host divides (0 / 0: no counted row gives NaN)
-    const double ne = 4.0 * (double)rec.rows;
-    ls->samples = rec.rows;
-    ls->skipped = rec.skipped;
-    ls->grad_surrogate = -recw.term / ne;
-    ls->grad = ls->grad_surrogate - (double)c->cfg.EntropyCoef;
-    ls->z2_mean = recw.zz / ne;
+  return WK_OK;
+}
+
+// this rank's shard: wk_policy_stats (ls null) and wk_log_std_gradient (the wide pass; out may be null)
+static int stats_impl(wk_ctx* c, wk_ppo_stats* out, float* logp_new, float* values_new,
+                      wk_log_std_grad* ls = nullptr) {
+  wk_ppo_sums s;
+  if (int r = sums_impl(c, ls != nullptr, &s, nullptr, logp_new, values_new)) return r;
+  if (out) wk_ppo_stats_from_sums(&s, out);
+  if (ls) wk_log_std_grad_from_sums(&s, c->cfg.EntropyCoef, ls);
+  return WK_OK;
+}
+
+int wk_policy_sums(wk_ctx* c, wk_ppo_sums* local, wk_ppo_sums* global) {
+  DevGuard dg_(c);
+  if (!c || !local) return WK_ERR_ARG;
+  const bool comm = c->comm || c->host_ar || c->ipc;
+  if (global && comm && !records_on(c)) {
+    SETERR(c, "wk_policy_sums: the global record needs the record exchange (wk_comm_records before the "
+              "communicator)");
+    return WK_ERR_STATE;
   }
+  if (int r = sums_impl(c, true, local, comm ? global : nullptr, nullptr, nullptr)) return r;
+  if (global && !comm) *global = *local;
+  return WK_OK;
+}
+
+int wk_policy_stats_global(wk_ctx* c, wk_ppo_stats* out) {
+  if (!c || !out) return WK_ERR_ARG;
+  wk_ppo_sums local, global;
+  if (int r = wk_policy_sums(c, &local, &global)) return r;
+  wk_ppo_stats_from_sums(&global, out);
   return WK_OK;
 }
 
@@ -428,16 +453,30 @@ static int ppo_update_impl(wk_ctx* c, const wk_ppo_args* args) {
     // LearnLogStd: the same pass, widened, yields the log-std's gradient as well (one pass per
     // epoch, not two); the step on the scalar comes before the stop decision, and g takes the new
     // std for the next epoch's gradient kernels
+    // On a record-exchange context the pass's record is gathered and folded over the ranks: the
+    // step and the decision are taken from the same bytes on every rank (one exchange per epoch).
     const bool learn = c->cfg.LearnLogStd == 1;
-    if (learn) {
+    const bool check = c->cfg.TargetKL > 0.0f;
+    if (records_on(c) && (learn || check)) {
+      wk_ppo_sums local, global;
+      if (int r = sums_impl(c, learn, &local, &global, nullptr, nullptr)) return r;
+      if (check) wk_ppo_stats_from_sums(&global, &c->upd_stats);
+      if (learn) {
+        wk_log_std_grad lg;
+        wk_log_std_grad_from_sums(&global, c->cfg.EntropyCoef, &lg);
+        log_std_step(c, lg);
+        g.std_ = c->P.std_;
+        g.lp_const = c->lp_const;
+      }
+    } else if (learn) {
       wk_log_std_grad lg;
-      if (int r = stats_impl(c, c->cfg.TargetKL > 0.0f ? &c->upd_stats : nullptr, nullptr, nullptr, &lg)) return r;
+      if (int r = stats_impl(c, check ? &c->upd_stats : nullptr, nullptr, nullptr, &lg)) return r;
       log_std_step(c, lg);
       g.std_ = c->P.std_;
       g.lp_const = c->lp_const;
     }
-    if (c->cfg.TargetKL > 0.0f) {
-      if (!learn)
+    if (check) {
+      if (!learn && !records_on(c))
         if (int r = stats_impl(c, &c->upd_stats, nullptr, nullptr)) return r;
       const bool stop = c->upd_stats.kl > (double)c->cfg.TargetKL;
       c->upd_stats.epochs_run = e + 1;

@@ -146,6 +146,19 @@ struct wk_ctx {
   wk_host_allreduce_fn host_ar = nullptr;  // wk_comm_init_host: a caller-supplied all-reduce
   void* host_ar_user = nullptr;
   std::vector<float> host_ar_buf;
+  // wk_comm_records: the exchange of statistics records (RX_*: declared kind; it runs once the
+  // matching communicator exists).  rx_dev [nranks][RECORD_WORDS] is the device gather buffer, this
+  // rank's record in slot `rank`; rx_err the device word k_rnorm_merge leaves a header mismatch in,
+  // read by the next synchronising call while rx_pending (an RCCL wk_rollout does not wait)
+  enum { RX_NONE = 0, RX_RCCL = 1, RX_HOST = 2 };
+  int rx_kind = RX_NONE;
+  wk_host_allgather_fn* rx_fn = nullptr;
+  void* rx_user = nullptr;
+  uint64_t rx_seq = 0;                 // record exchanges so far (the header's sequence)
+  unsigned long long* rx_dev = nullptr;
+  uint32_t* rx_err = nullptr;
+  bool rx_pending = false;
+  std::vector<uint64_t> rx_host;       // [nranks][RECORD_WORDS] on the host
   // wk_comm_init_ipc: the one-shot exchange over peer-mapped memory (k_reduce_xch_adam)
   void* xch = nullptr;                 // this rank's exchange region (exported by IPC handle)
   std::vector<void*> xch_peers;        // peers' regions, opened from their handles
@@ -292,6 +305,19 @@ int comm_exchange(wk_ctx* c);
 int xch_status(wk_ctx* c);
 int xch_mark_t(wk_ctx* c);
 void comm_close(wk_ctx* c);
+// the record exchange (wk_comm_records).  records_on: declared and the communicator exists.
+// rx_header: the next exchange's header word (advances the sequence).  rx_gather_device: this
+// rank's record in its slot of rx_dev -> every rank's in rx_dev (RCCL: stream-ordered, no wait, the
+// header check left to the consumer kernel and rx_deferred; host: checked here).  rx_gather_host:
+// the same, then every rank's record on the host in c->rx_host, headers checked (it synchronises).
+// rx_deferred: the pending header check of an RCCL reward-normalisation exchange (it synchronises).
+inline bool records_on(const wk_ctx* c) {
+  return c->rx_kind != wk_ctx::RX_NONE && (c->comm != nullptr || c->host_ar != nullptr);
+}
+uint64_t rx_header(wk_ctx* c, int kind);
+int rx_gather_device(wk_ctx* c, uint64_t header);
+int rx_gather_host(wk_ctx* c, uint64_t header);
+int rx_deferred(wk_ctx* c);
 // wk_api_io.cpp
 bool write_file(const char* path, const void* data, size_t n);
 

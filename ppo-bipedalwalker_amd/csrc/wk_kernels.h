@@ -307,6 +307,25 @@ hipError_t launch_rnorm_pass(int n, int T, float gamma, float clip, float epsilo
                              const float* r, const uint8_t* done, float* acc,
                              unsigned long long* partial, RnormRec* rec, float* out, hipStream_t s);
 hipError_t launch_rnorm_reset(int n, const uint8_t* mask, float* acc, hipStream_t s);
+// The full pass on a record-exchange context (wk_comm_records), in two halves around the gather.
+// A record is RECORD_WORDS 64-bit words, word 0 its header; `slot` is this rank's record in the
+// device gather buffer all[nranks][RECORD_WORDS].
+//   launch_rnorm_batch  scan, then k_rnorm_batch: the tiles' partials folded with k_rnorm_finish's
+//                       association into (count, bad, sum x, sum x^2) behind the header in slot
+//   launch_rnorm_merge  k_rnorm_merge: the ranks' records folded in rank order from rank 0's and
+//                       merged into rec with k_rnorm_finish's arithmetic (a record whose header is
+//                       not `header` puts its rank + 1 in *err and nothing is merged), then apply
+enum : int { RECORD_WORDS = 16 };
+hipError_t launch_rnorm_batch(int n, int T, float gamma, const float* r, const uint8_t* done, float* acc,
+                              unsigned long long* partial, unsigned long long header,
+                              unsigned long long* slot, hipStream_t s);
+hipError_t launch_rnorm_merge(int n, int T, float clip, float epsilon, const unsigned long long* all,
+                              int nranks, unsigned long long header, uint32_t* err, const float* r,
+                              RnormRec* rec, float* out, hipStream_t s);
+// `nwords` words of a device record behind `header` into a gather slot, the rest of the slot zero
+// (the statistics' record on its way to the exchange)
+hipError_t launch_record_pack(const void* src, int nwords, unsigned long long header,
+                              unsigned long long* slot, hipStream_t s);
 
 // ---- wk_net.hip
 // the general networks' kernels (wk_net.hip; NetworkKernels = 1).  nets: device copy of

@@ -15,6 +15,11 @@
 //                   copysignf (a NaN stays), float4 where the buffers are aligned; the scale is
 //                   read from the device record, the clamped rows are counted with integer adds.
 //
+// On a record-exchange context (wk_comm_records) the finish step is split around the gather of the
+// ranks' batch records: k_rnorm_batch folds the tiles' partials into this rank's record, with the
+// fold k_rnorm_finish uses, and k_rnorm_merge folds the ranks' records in rank order and merges
+// the result with the arithmetic k_rnorm_finish uses -- one rank gives k_rnorm_finish's bytes.
+//
 // No floating-point atomics: a tile's association is the tree, the tiles are summed in tile order,
 // and a tile is RNORM_TILE consecutive walkers whatever the grid, so the same inputs give the
 // same bytes.
@@ -32,6 +37,63 @@ __device__ __forceinline__ void rnorm_tree(V* sh, int tid) {
     if (tid < s) sh[tid] = sh[tid] + sh[tid + s];
     __syncthreads();
   }
+}
+
+// a batch's samples: count, non-finite count, sum x, sum x^2
+struct RnormBatch {
+  long long cnt, bad;
+  double s1, s2;
+};
+
+// The tiles' partials folded by one block of RNORM_TILE lanes: lane i takes tiles i, i + TILE, ...
+// in that order, then the tree over the lanes.  Every lane calls it and gets the result.
+__device__ __forceinline__ RnormBatch rnorm_fold_tiles(const unsigned long long* __restrict__ partial,
+                                                       int ntiles, int tid) {
+  __shared__ double sh_s1[RNORM_TILE], sh_s2[RNORM_TILE];
+  __shared__ long long sh_cnt[RNORM_TILE], sh_bad[RNORM_TILE];
+  long long cnt = 0, bad = 0;
+  double s1 = 0.0, s2 = 0.0;
+  for (int j = tid; j < ntiles; j += RNORM_TILE) {
+    const unsigned long long* p = partial + (size_t)j * RNORM_FIELDS;
+    cnt += (long long)p[0];
+    bad += (long long)p[1];
+    s1 += __longlong_as_double((long long)p[2]);
+    s2 += __longlong_as_double((long long)p[3]);
+  }
+  sh_s1[tid] = s1; sh_s2[tid] = s2; sh_cnt[tid] = cnt; sh_bad[tid] = bad;
+  __syncthreads();
+  rnorm_tree(sh_s1, tid);
+  rnorm_tree(sh_s2, tid);
+  rnorm_tree(sh_cnt, tid);
+  rnorm_tree(sh_bad, tid);
+  return RnormBatch{sh_cnt[0], sh_bad[0], sh_s1[0], sh_s2[0]};
+}
+
+// One thread: the batch merged into the running (count, mean, m2) by Chan's formula in double, the
+// new scale, and the pass's counters (`bad` the batch's non-finite samples).
+__device__ __forceinline__ void rnorm_merge_store(const RnormBatch& b, float epsilon, long long rows,
+                                                  RnormRec* __restrict__ rec) {
+  const long long cnt_b = b.cnt;
+  long long count = rec->count;
+  double mean = rec->mean, m2 = rec->m2;
+  if (cnt_b > 0) {
+    const double nb = (double)cnt_b, na = (double)count;
+    const double mean_b = b.s1 / nb;
+    const double m2_b = fmax(0.0, b.s2 - b.s1 * mean_b);
+    const double delta = mean_b - mean, tot = na + nb;
+    mean += delta * nb / tot;
+    m2 += m2_b + delta * delta * na * nb / tot;
+    count += cnt_b;
+  }
+  const double var = count > 0 ? m2 / (double)count : 0.0;
+  float scale = 1.0f;
+  if (count > 0) {
+    const float sc = (float)(1.0 / sqrt(var + (double)epsilon));
+    if (__builtin_isfinite(sc) && sc > 0.0f) scale = sc;
+  }
+  rec->count = count; rec->mean = mean; rec->m2 = m2; rec->var = var;
+  rec->scale = scale;
+  rec->rows = rows; rec->clipped = 0; rec->nonfinite = b.bad;
 }
 }  // namespace
 
@@ -108,46 +170,61 @@ void k_rnorm_finish(const unsigned long long* __restrict__ partial, int ntiles, 
     if (tid == 0) { rec->rows = rows; rec->clipped = 0; rec->nonfinite = 0; }
     return;
   }
-  __shared__ double sh_s1[RNORM_TILE], sh_s2[RNORM_TILE];
-  __shared__ long long sh_cnt[RNORM_TILE], sh_bad[RNORM_TILE];
-  long long cnt = 0, bad = 0;
-  double s1 = 0.0, s2 = 0.0;
-  // lane i takes tiles i, i + TILE, ... in that order, then the tree over the lanes
-  for (int j = tid; j < ntiles; j += RNORM_TILE) {
-    const unsigned long long* p = partial + (size_t)j * RNORM_FIELDS;
-    cnt += (long long)p[0];
-    bad += (long long)p[1];
-    s1 += __longlong_as_double((long long)p[2]);
-    s2 += __longlong_as_double((long long)p[3]);
+  const RnormBatch b = rnorm_fold_tiles(partial, ntiles, tid);
+  if (tid == 0) rnorm_merge_store(b, epsilon, rows, rec);
+}
+
+// this rank's batch record behind its header, the rest of the slot zero (plain vector stores)
+__global__ __launch_bounds__(RNORM_TILE)
+void k_rnorm_batch(const unsigned long long* __restrict__ partial, int ntiles, unsigned long long header,
+                   unsigned long long* __restrict__ slot) {
+  const int tid = threadIdx.x;
+  const RnormBatch b = rnorm_fold_tiles(partial, ntiles, tid);
+  if (tid >= RECORD_WORDS) return;
+  unsigned long long w = 0ull;
+  if (tid == 0) w = header;
+  if (tid == 1) w = (unsigned long long)b.cnt;
+  if (tid == 2) w = (unsigned long long)b.bad;
+  if (tid == 3) w = (unsigned long long)__double_as_longlong(b.s1);
+  if (tid == 4) w = (unsigned long long)__double_as_longlong(b.s2);
+  slot[tid] = w;
+}
+
+// One thread: the ranks' batch records folded in rank order, starting from rank 0's, then
+// k_rnorm_finish's merge.  Every rank runs this on the same bytes and stores the same statistics.
+__global__ __launch_bounds__(64)
+void k_rnorm_merge(const unsigned long long* __restrict__ all, int nranks, unsigned long long header,
+                   float epsilon, long long rows, uint32_t* __restrict__ err, RnormRec* __restrict__ rec) {
+  if (threadIdx.x != 0) return;
+  for (int r = 0; r < nranks; r++)
+    if (all[(size_t)r * RECORD_WORDS] != header) {  // a peer in another exchange: nothing is merged
+      err[0] = (uint32_t)r + 1u;
+      rec->rows = rows; rec->clipped = 0; rec->nonfinite = 0;
+      return;
+    }
+  const auto rd = [&](int r) {
+    const unsigned long long* p = all + (size_t)r * RECORD_WORDS + 1;
+    return RnormBatch{(long long)p[0], (long long)p[1], __longlong_as_double((long long)p[2]),
+                      __longlong_as_double((long long)p[3])};
+  };
+  RnormBatch b = rd(0);
+  for (int r = 1; r < nranks; r++) {
+    const RnormBatch x = rd(r);
+    b.cnt += x.cnt;
+    b.bad += x.bad;
+    b.s1 += x.s1;
+    b.s2 += x.s2;
   }
-  sh_s1[tid] = s1; sh_s2[tid] = s2; sh_cnt[tid] = cnt; sh_bad[tid] = bad;
-  __syncthreads();
-  rnorm_tree(sh_s1, tid);
-  rnorm_tree(sh_s2, tid);
-  rnorm_tree(sh_cnt, tid);
-  rnorm_tree(sh_bad, tid);
-  if (tid != 0) return;
-  const long long cnt_b = sh_cnt[0];
-  long long count = rec->count;
-  double mean = rec->mean, m2 = rec->m2;
-  if (cnt_b > 0) {
-    const double nb = (double)cnt_b, na = (double)count;
-    const double mean_b = sh_s1[0] / nb;
-    const double m2_b = fmax(0.0, sh_s2[0] - sh_s1[0] * mean_b);
-    const double delta = mean_b - mean, tot = na + nb;
-    mean += delta * nb / tot;
-    m2 += m2_b + delta * delta * na * nb / tot;
-    count += cnt_b;
-  }
-  const double var = count > 0 ? m2 / (double)count : 0.0;
-  float scale = 1.0f;
-  if (count > 0) {
-    const float sc = (float)(1.0 / sqrt(var + (double)epsilon));
-    if (__builtin_isfinite(sc) && sc > 0.0f) scale = sc;
-  }
-  rec->count = count; rec->mean = mean; rec->m2 = m2; rec->var = var;
-  rec->scale = scale;
-  rec->rows = rows; rec->clipped = 0; rec->nonfinite = sh_bad[0];
+  rnorm_merge_store(b, epsilon, rows, rec);
+}
+
+// `nwords` words behind the header into a gather slot, the rest zero
+__global__ __launch_bounds__(64)
+void k_record_pack(const unsigned long long* __restrict__ src, int nwords, unsigned long long header,
+                   unsigned long long* __restrict__ slot) {
+  const int tid = threadIdx.x;
+  if (tid >= RECORD_WORDS) return;
+  slot[tid] = tid == 0 ? header : (tid <= nwords ? src[tid - 1] : 0ull);
 }
 
 __device__ __forceinline__ float rnorm_scaled(float r, float scale, float clip, int& clipped) {
@@ -193,6 +270,17 @@ __global__ void k_rnorm_reset(int n, const uint8_t* __restrict__ mask, float* __
 
 int rnorm_tiles(int n) { return (n + RNORM_TILE - 1) / RNORM_TILE; }
 
+// the apply step over `rows` rewards with the scale rec holds
+static void launch_rnorm_apply(long long rows, float clip, const float* r, RnormRec* rec, float* out,
+                               hipStream_t s) {
+  const bool aligned = (((uintptr_t)r | (uintptr_t)out) & 15) == 0;
+  const long long nvec = aligned ? rows / 4 : 0;
+  const long long lanes = nvec > rows - 4 * nvec ? nvec : rows - 4 * nvec;
+  const long long nb = (lanes + 255) / 256;
+  hipLaunchKernelGGL(k_rnorm_apply, dim3((unsigned)(nb < 1 ? 1 : (nb > 65536 ? 65536 : nb))), dim3(256), 0, s,
+                     rows, nvec, clip, r, rec, out);
+}
+
 hipError_t launch_rnorm_pass(int n, int T, float gamma, float clip, float epsilon, bool learn,
                              const float* r, const uint8_t* done, float* acc,
                              unsigned long long* partial, RnormRec* rec, float* out, hipStream_t s) {
@@ -202,12 +290,34 @@ hipError_t launch_rnorm_pass(int n, int T, float gamma, float clip, float epsilo
   if (learn) hipLaunchKernelGGL(k_rnorm_scan, dim3(ntiles), dim3(RNORM_TILE), 0, s, n, T, gamma, r, done, acc, partial);
   hipLaunchKernelGGL(k_rnorm_finish, dim3(1), dim3(RNORM_TILE), 0, s, partial, ntiles, learn ? 1 : 0,
                      epsilon, rows, rec);
-  const bool aligned = (((uintptr_t)r | (uintptr_t)out) & 15) == 0;
-  const long long nvec = aligned ? rows / 4 : 0;
-  const long long lanes = nvec > rows - 4 * nvec ? nvec : rows - 4 * nvec;
-  const long long nb = (lanes + 255) / 256;
-  hipLaunchKernelGGL(k_rnorm_apply, dim3((unsigned)(nb < 1 ? 1 : (nb > 65536 ? 65536 : nb))), dim3(256), 0, s,
-                     rows, nvec, clip, r, rec, out);
+  launch_rnorm_apply(rows, clip, r, rec, out, s);
+  return hipGetLastError();
+}
+
+hipError_t launch_rnorm_batch(int n, int T, float gamma, const float* r, const uint8_t* done, float* acc,
+                              unsigned long long* partial, unsigned long long header,
+                              unsigned long long* slot, hipStream_t s) {
+  if (n <= 0 || T <= 0) return hipErrorInvalidValue;
+  const int ntiles = rnorm_tiles(n);
+  hipLaunchKernelGGL(k_rnorm_scan, dim3(ntiles), dim3(RNORM_TILE), 0, s, n, T, gamma, r, done, acc, partial);
+  hipLaunchKernelGGL(k_rnorm_batch, dim3(1), dim3(RNORM_TILE), 0, s, partial, ntiles, header, slot);
+  return hipGetLastError();
+}
+
+hipError_t launch_rnorm_merge(int n, int T, float clip, float epsilon, const unsigned long long* all,
+                              int nranks, unsigned long long header, uint32_t* err, const float* r,
+                              RnormRec* rec, float* out, hipStream_t s) {
+  if (n <= 0 || T <= 0 || nranks <= 0) return hipErrorInvalidValue;
+  const long long rows = (long long)n * T;
+  hipLaunchKernelGGL(k_rnorm_merge, dim3(1), dim3(64), 0, s, all, nranks, header, epsilon, rows, err, rec);
+  launch_rnorm_apply(rows, clip, r, rec, out, s);
+  return hipGetLastError();
+}
+
+hipError_t launch_record_pack(const void* src, int nwords, unsigned long long header,
+                              unsigned long long* slot, hipStream_t s) {
+  if (nwords < 0 || nwords >= RECORD_WORDS) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_record_pack, dim3(1), dim3(64), 0, s, (const unsigned long long*)src, nwords, header, slot);
   return hipGetLastError();
 }
 

@@ -53,7 +53,11 @@ EXPORTS = [
     "wk_reward_norm_defaults", "wk_reward_norm_config", "wk_reward_norm_get", "wk_reward_norm_set",
     "wk_reward_norm_get_acc", "wk_reward_norm_set_acc", "wk_reward_norm_update", "wk_get_scaled_rewards",
     "wk_render_defaults", "wk_render", "wk_render_device", "wk_render_states",
+    "wk_comm_records", "wk_ppo_sums_add", "wk_ppo_stats_from_sums", "wk_log_std_grad_from_sums",
+    "wk_policy_sums", "wk_policy_stats_global",
 ]
+COMM_RECORD_WORDS = 16  # WK_COMM_RECORD_WORDS: one record of the record exchange, 64-bit words
+RECORD_STATS, RECORD_REWARD_NORM = 1, 2  # the kinds in a record's header word
 
 
 def check_state(state):
@@ -188,6 +192,48 @@ class PpoStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PpoSums(C.Structure):
+    """wk_ppo_sums: the raw sums the statistics passes end in (wk_policy_sums), as the record
+    exchange gathers them and the host divides them"""
+    _fields_ = [("rows", C.c_int64), ("skipped", C.c_int64), ("clipped", C.c_int64),
+                ("kl", C.c_double), ("k1", C.c_double), ("surr", C.c_double), ("sr", C.c_double),
+                ("srr", C.c_double), ("se", C.c_double), ("see", C.c_double), ("rmax", C.c_double),
+                ("term", C.c_double), ("zz", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+PPO_SUMS = PpoSums
+
+
+def _sums(s):
+    """a PpoSums from a PpoSums or its dict"""
+    return s if isinstance(s, PpoSums) else PpoSums(**{k: s[k] for k, _ in PpoSums._fields_})
+
+
+def sums_add(acc, x):
+    """wk_ppo_sums_add: acc + x as a new dict (integers and doubles add, rmax is the larger, a NaN
+    stays) -- the fold step of the record exchange, so the order of a chain of calls matters"""
+    a = PpoSums.from_buffer_copy(_sums(acc))
+    load_library().wk_ppo_sums_add(C.byref(a), C.byref(_sums(x)))
+    return a.as_dict()
+
+
+def stats_from_sums(s):
+    """wk_ppo_stats_from_sums: the statistics' dict (policy_stats' keys) from the raw sums"""
+    st = PpoStats()
+    load_library().wk_ppo_stats_from_sums(C.byref(_sums(s)), C.byref(st))
+    return st.as_dict()
+
+
+def log_std_grad_from_sums(s, entropy_coef=0.0):
+    """wk_log_std_grad_from_sums: the log-std gradient's dict (log_std_gradient's keys)"""
+    g = LogStdGrad()
+    load_library().wk_log_std_grad_from_sums(C.byref(_sums(s)), float(entropy_coef), C.byref(g))
+    return g.as_dict()
 
 
 class GradNorms(C.Structure):
@@ -330,6 +376,8 @@ class Profile(C.Structure):
 _lib = None
 # wk_host_allreduce_fn: int (*)(float* buf, int n, void* user)
 HOST_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p)
+# wk_host_allgather_fn: int (const uint64_t* mine, uint64_t* all, void* user)
+HOST_ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p)
 
 
 def load_library(path=None):
@@ -458,6 +506,12 @@ def load_library(path=None):
         "wk_render": (I, [P, C.POINTER(RenderArgs), P, I, P]),
         "wk_render_device": (I, [P, C.POINTER(RenderArgs), P, I, P]),
         "wk_render_states": (I, [P, C.POINTER(RenderArgs), P, P, I, P]),
+        "wk_comm_records": (I, [P, P, P]),
+        "wk_ppo_sums_add": (None, [C.POINTER(PpoSums), C.POINTER(PpoSums)]),
+        "wk_ppo_stats_from_sums": (None, [C.POINTER(PpoSums), C.POINTER(PpoStats)]),
+        "wk_log_std_grad_from_sums": (None, [C.POINTER(PpoSums), F, C.POINTER(LogStdGrad)]),
+        "wk_policy_sums": (I, [P, C.POINTER(PpoSums), C.POINTER(PpoSums)]),
+        "wk_policy_stats_global": (I, [P, C.POINTER(PpoStats)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -616,6 +670,9 @@ class Engine:
             if rc == WK_ERR_COMM and getattr(self, "_host_ar_error", None):
                 msg += f" [host all-reduce callback raised {self._host_ar_error}; fatal for the job]"
                 self._host_ar_error = None
+            if rc == WK_ERR_COMM and getattr(self, "_rx_error", None):
+                msg += f" [record all-gather callback raised {self._rx_error}; fatal for the job]"
+                self._rx_error = None
             raise WkError(msg)
 
     def close(self):
@@ -876,6 +933,23 @@ class Engine:
         T = (st.samples + st.skipped) // self.n
         return st.as_dict(), lp[:T], v[:T]
 
+    def policy_sums(self, global_=False):
+        """wk_policy_sums: the raw sums of the log-std pass over this rank's trajectory buffer as a
+        dict.  global_=True returns (local, global): on a record-exchange context (comm_records) a
+        COLLECTIVE call whose second dict is the ranks' records folded in rank order, the same
+        bytes on every rank; on a context with no communicator the local record twice"""
+        loc, glo = PpoSums(), PpoSums()
+        self._chk(self.lib.wk_policy_sums(self.h, C.byref(loc), C.byref(glo) if global_ else None),
+                  "wk_policy_sums")
+        return (loc.as_dict(), glo.as_dict()) if global_ else loc.as_dict()
+
+    def policy_stats_global(self):
+        """wk_policy_stats_global: policy_stats' dict over all the ranks' shards (collective on a
+        record-exchange context; this context's own without a communicator)"""
+        st = PpoStats()
+        self._chk(self.lib.wk_policy_stats_global(self.h, C.byref(st)), "wk_policy_stats_global")
+        return st.as_dict()
+
     def update_stats(self):
         """wk_update_stats_get: the last per-epoch check of the last ppo_update of a TargetKL > 0
         context (with epochs_run and stopped_early) as a dict"""
@@ -1063,7 +1137,37 @@ class Engine:
             raise WkError(f"wk_comm_unique_id failed: {lib.wk_last_error(None).decode()}")
         return bytes(buf)
 
+    def comm_records(self, gather=None):
+        """wk_comm_records, before comm_init / comm_init_host: the ranks exchange their statistics
+        records, so TargetKL, LearnLogStd and reward normalisation run on any number of GPUs.
+        gather=None: RCCL (then comm_init).  A callable (then comm_init_host) receives this rank's
+        record, uint64[16], and returns every rank's, uint64[nranks, 16] in rank order
+        (wk.dist.gather_records over torch.distributed); it is kept alive here.  A callback that
+        raises, or returns another shape, fails the call in progress with WK_ERR_COMM: fatal for
+        the whole job, like a failed all-reduce."""
+        self._rx_error = None
+        if gather is None:
+            self._rx_fn = None
+            self._chk(self.lib.wk_comm_records(self.h, None, None), "wk_comm_records")
+            return
+
+        def _cb(mine, out, user):
+            try:
+                n = getattr(self, "_nranks", 1)
+                res = np.ascontiguousarray(gather(np.ctypeslib.as_array(mine, shape=(COMM_RECORD_WORDS,)).copy()),
+                                           dtype=np.uint64)
+                if res.shape != (n, COMM_RECORD_WORDS):
+                    raise ValueError(f"the gather returned shape {res.shape}, not ({n}, {COMM_RECORD_WORDS})")
+                np.ctypeslib.as_array(out, shape=(n, COMM_RECORD_WORDS))[:] = res
+                return 0
+            except Exception as ex:  # noqa: BLE001 -- reported as WK_ERR_COMM by the library
+                self._rx_error = f"{type(ex).__name__}: {ex}"
+                return 1
+        self._rx_fn = HOST_ALLGATHER_FN(_cb)
+        self._chk(self.lib.wk_comm_records(self.h, C.cast(self._rx_fn, C.c_void_p), None), "wk_comm_records")
+
     def comm_init(self, rank, nranks, uid):
+        self._nranks = int(nranks)
         buf = (C.c_uint8 * 128).from_buffer_copy(uid)
         self._chk(self.lib.wk_comm_init(self.h, int(rank), int(nranks), buf), "wk_comm_init")
 
@@ -1075,6 +1179,7 @@ class Engine:
         must be treated as fatal for the whole job (let it propagate so the launcher tears the
         process group down; the ranks' replicas have diverged)."""
         self._host_ar_error = None
+        self._nranks = int(nranks)
 
         def _cb(buf, n, user):
             try:

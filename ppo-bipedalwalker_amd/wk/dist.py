@@ -1,8 +1,10 @@
 """Multi-GPU sharding for the walker engine (one process per GPU).
 
 Walkers are independent (each owns its floor copy, Environment.cs:27,43-48), so env
-ranges shard with no data-path collective; the only exchange is the RCCL all-reduce
-of the flat 6,149-float policy gradient per minibatch inside wk_ppo_update (each rank
+ranges shard with no data-path collective; the exchanges are the RCCL all-reduce
+of the flat 6,149-float policy gradient per minibatch inside wk_ppo_update and, where
+TargetKL, LearnLogStd or reward normalisation are on, the all-gather of one 16-word
+statistics record per epoch / rollout (Engine.comm_records, gather_records) (each rank
 scales its per-sample gradients by 1/global minibatch, so the sum is the reference's
 sum / BatchSize over the global minibatch).  Adam then runs replicated on every rank
 from identically seeded weights (no broadcast).
@@ -63,3 +65,19 @@ def gather_episode_log(recs, group=None):
     dist.all_gather_object(parts, np.asarray(recs, EPISODE_DTYPE).tobytes(), group=group)
     allr = np.concatenate([np.frombuffer(b, EPISODE_DTYPE) for b in parts])
     return allr[np.lexsort((allr["env"], allr["step"]))]
+
+
+def gather_records(group=None):
+    """The callback Engine.comm_records takes, over torch.distributed.all_gather on CPU tensors (any
+    backend's control plane): this rank's record, uint64[16], in; every rank's, uint64[nranks, 16]
+    in rank order, out.  Every rank receives every record byte for byte and folds them itself."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+
+    def gather(mine):
+        t = torch.from_numpy(np.ascontiguousarray(mine, np.uint64).view(np.int64).copy())
+        parts = [torch.empty_like(t) for _ in range(dist.get_world_size(group))]
+        dist.all_gather(parts, t, group=group)
+        return np.stack([p.numpy() for p in parts]).view(np.uint64)
+    return gather
